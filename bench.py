@@ -15,11 +15,18 @@ replaced by new ones (game g seeded MT19937(g)).
 Steady state, whatever --warmup says: all slots start at ply 0 together
 and the shared transposition cache (the reference's plays_inferences)
 starts empty, so the first moves are not representative.  Untimed moves
-run until at least --warmup moves have passed AND the cache is full and has
-taken 1.5x its capacity in inserts (least-recently-used eviction, az_tree.h:
-its content and hit rate are then stationary, profiles/r6/cache_curve*) --
-every one of them real work.  The line states the cache's capacity, fill,
-generation, age in moves and the window's hit rate.
+run until at least --warmup moves have passed AND the cache is 95% full and
+has taken 1.2x its capacity in inserts (least-recently-used eviction,
+az_tree.h): from there on its hit rate and the step time are stationary
+(profiles/r6/cache_curve.py at configs[1]: 0.887-0.893 and 14.7-14.8 ms per
+move in every 50-move window from move 1200 to 1800; the
+rule first holds near move 1235, a third earlier than the 1.5x / 98% rule
+that ends in the same state) -- every one of them real work.  Their number
+is fixed by the arguments, 7.7 x capacity / (slots x sims) = 1262 here, so
+every run times the same moves; the rule is checked after them and only
+adds blocks of 64 moves where it does not hold yet.  The line
+states the cache's capacity, fill, generation, age in moves and the
+window's hit rate.
 value = games drained in the K timed steps, summed over ranks / max-over-
 ranks wall time.
 
@@ -29,7 +36,15 @@ reach the other ranks by one RCCL broadcast over xGMI before timing, and
 the games each rank finished in the window are gathered to rank 0 (compact
 int8 boards + f64 policies, RCCL) right after it.
 
-The CPU baselines (rank 0, N=1 only) are oracle/refport.py -- the
+A plain run does what the headline needs and no more: set up, the untimed
+moves, the K timed steps, --dump-outputs DIR (the games those steps
+delivered, as DIR/<name>.npy: the same arguments give the same games, so
+two builds can be compared array for array) and the line.  --full adds the
+CPU baselines, a window that times the tree kernels, a window with the
+cache bypassed and the tower's isolated forwards; their fields are null
+without it.
+
+The CPU baselines (--full; rank 0, N=1 only) are oracle/refport.py -- the
 reference's self-play structure, pinned to the reference by
 tests/test_refport.py -- run before the GPU is touched: the reference's
 joblib fan-out (one game per worker process, 1-thread torch-CPU network,
@@ -63,8 +78,10 @@ F16_MFMA_PEAK_TFLOPS = 2500.0   # MI355X_MICROARCH.md: dense bf16/fp16 MFMA (no 
 MIN_PREROLL = 24                # untimed moves at least (game-completion rate stationary, ~1 game length)
 MAX_PREROLL = 4000
 WINDOW_EVENT_STRIDE = 1         # the timed window's tower events: every launch of each lane
-CACHE_TURNOVER = 1.5            # cache inserts / capacity before the window (full table turned over: stationary)
-CACHE_FULL = 0.98               # ... and the table this full
+CACHE_TURNOVER = 1.2            # cache inserts / capacity before the window (full table turned over: stationary)
+CACHE_FULL = 0.95               # ... and the table this full
+UNTIMED_PER_TURNOVER = 7.7      # untimed moves x slots x sims / capacity (configs[1]: the rule first holds at 7.53)
+UNTIMED_BLOCK = 64              # further untimed moves at a time while the rule does not hold yet
 
 
 def parse():
@@ -110,6 +127,13 @@ def parse():
     ap.add_argument("--share-devices", action="store_true",
                     help="rehearsal: allow more ranks than visible GPUs (ranks share devices; "
                          "the line reports shared_devices)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the CPU baselines (--no-cpu-baseline skips "
+                         "them), the tree-kernel window, the cache-bypassed window (--no-cache-window skips it) "
+                         "and the isolated forwards; without it their fields are null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the games the timed steps delivered to the host (rank 0's, ordered by game id) "
+                         "as DIR/<name>.npy, float32/float64, at most 64 MB")
     args = ap.parse_args()
     chess = args.game == "chess"
     for k, c4, ch in (("steps", 30, 3), ("warmup", 5, 2), ("slots", 4096, 256), ("sims", 100, 800),
@@ -438,7 +462,7 @@ def chess_main(args):
     spec = weight_spec(8, 8, 1880, depth=args.depth, in_channels=118)
     host_w = init_weights(spec, seed=0)
     base = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         base = chess_cpu_baseline(args, host_w)
     import torch
     import torch.distributed as dist
@@ -480,6 +504,9 @@ def chess_main(args):
     eng.timer(False)
     window = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
     drained = len(window["lengths"])
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, window)
     # ---- N>1: the window's chess games to rank 0 (replay-buffer gather; a
     # chess game outlasts a short window, so often none -- the path runs anyway)
     gather = None
@@ -559,6 +586,8 @@ def chess_main(args):
             "games_drained_basis": "games whose records reached the host in the window (az_chess_selfplay_drain "
                                    "after every asynchronous step, and once more after the final synchronize)",
             "replay_buffer_gather": gather,
+            "full": bool(args.full),
+            "dump_outputs": dumped,
             "lanes": args.lanes or "auto",
             "roofline": roof,
             "cpu_baseline": base,
@@ -576,16 +605,64 @@ class WindowGames:
 
     def __init__(self):
         self.parts = []
+        self.empty = None   # a drain that returned no game: the arrays' shapes
 
     def add(self, d):
         if len(d["lengths"]):
             self.parts.append(d)
+        else:
+            self.empty = d
+
+    def drained(self):
+        """Every array selfplay_drain returned, over the window (--dump-outputs)."""
+        if not self.parts:
+            return self.empty
+        return {k: np.concatenate([p[k] for p in self.parts]) for k in self.parts[0]}
 
     def results(self):
         if not self.parts:
             return None
         return {k: np.concatenate([p[k] for p in self.parts]) for k in
                 ("lengths", "results", "expansions", "boards", "policies", "moves")}
+
+
+DUMP_MAX_BYTES = 64 << 20       # --dump-outputs: all files together
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(dirname, games):
+    """--dump-outputs: the games the timed steps delivered (the dicts
+    selfplay_drain returned in the window, concatenated) as one .npy per
+    array, float32 (float64 for 8-byte fields), rows ordered by game id.
+
+    A step's drain returns the games of the newest finished move, so how
+    the window's games split over its drains depends on timing; their union
+    does not (game g is seeded by g and finishes at a fixed move), hence the
+    whole window ordered by game id and not the last drain alone.  Rows past
+    a game's length carry no sample and are written as zeros.  Above
+    DUMP_MAX_BYTES a seeded sample of the games (the same for the same
+    count) is kept."""
+    os.makedirs(dirname, exist_ok=True)
+    order = np.argsort(games["game_ids"], kind="stable")
+    out = {}
+    for k, v in games.items():
+        if v.dtype.fields is not None:  # packed records (chess positions): their bytes
+            v = v.view(np.uint8).reshape(v.shape + (v.dtype.itemsize,))
+        out[k] = v[order].astype(np.float64 if v.dtype.itemsize == 8 else np.float32)
+    n = len(order)
+    plies = np.arange(out["moves"].shape[1])[None, :] >= games["lengths"][order][:, None]
+    for k, v in out.items():
+        if v.ndim >= 2 and v.shape[1] == plies.shape[1]:
+            v[plies] = 0
+    per_game = sum(v[:1].nbytes for v in out.values()) if n else 0
+    keep = DUMP_MAX_BYTES // max(per_game, 1)
+    if n > keep:
+        pick = np.sort(np.random.RandomState(DUMP_SAMPLE_SEED).choice(n, keep, replace=False))
+        out = {k: v[pick] for k, v in out.items()}
+    for k, v in out.items():
+        np.save(os.path.join(dirname, k + ".npy"), v)
+    return {"dir": dirname, "games": int(min(n, keep)), "of": int(n),
+            "bytes": int(sum(v.nbytes for v in out.values())), "arrays": sorted(out)}
 
 
 def step_and_drain(eng, sink=None):
@@ -595,6 +672,22 @@ def step_and_drain(eng, sink=None):
     if sink is not None:
         sink.add(d)
     return st, len(d["lengths"])
+
+
+def untimed_moves_planned(args, st):
+    """The untimed moves, a number fixed by the arguments, so that the timed
+    steps start from the same position in every run (--dump-outputs relies
+    on it): max(--warmup, MIN_PREROLL) and, with the cache on,
+    UNTIMED_PER_TURNOVER x capacity / (slots x sims).  The cache's own
+    counters vary by a few thousand entries from run to run (lookups race
+    with evictions), and so does the move at which they cross CACHE_FULL /
+    CACHE_TURNOVER (1234 and 1235 in two runs of configs[1]); main() checks
+    the rule after these moves and only if it does not hold yet adds
+    UNTIMED_BLOCK moves at a time until it does."""
+    moves = max(args.warmup, MIN_PREROLL)
+    if args.cache_log2 and st["cache_gen_size"]:
+        moves = max(moves, int(-(-UNTIMED_PER_TURNOVER * st["cache_capacity"] // (args.slots * args.sims))))
+    return min(moves, MAX_PREROLL)
 
 
 def launch_ranks(args):
@@ -698,8 +791,9 @@ def main():
     spec = weight_spec(args.height, args.width, A, depth=args.depth)
     host_w = init_weights(spec, seed=0)
 
+    t_start = time.perf_counter()
     base = base0 = native = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         base = cpu_baseline(args, host_w)
         native = cpu_baseline_native(args, host_w)
         if (args.height, args.width, args.n) == (6, 7, 4) and args.cpu_configs0_seconds > 0:
@@ -731,10 +825,18 @@ def main():
     eng.selfplay_begin(first_game=rank * budget, n_games=budget, base_seed=0)
 
     # ---- untimed: at least --warmup moves, until the cache is stationary
+    # in the window's form (enqueue move m, drain move m - 1); the rule is
+    # looked at (a synchronize) after the planned moves, then after every block
+    t_untimed = time.perf_counter()
     pre = 0
+    ahead = untimed_moves_planned(args, eng.stats())
     while True:
-        st, _ = step_and_drain(eng)
-        pre += 1
+        for _ in range(ahead):
+            eng.selfplay_step(1, sync=False)
+            eng.selfplay_drain()
+            pre += 1
+        ahead = min(UNTIMED_BLOCK, MAX_PREROLL - pre)
+        st = eng.stats()
         gen_ok = (not args.cache_log2 or not st["cache_gen_size"]
                   or (st["cache_inserts"] >= CACHE_TURNOVER * st["cache_capacity"]
                       and st["cache_entries"] >= CACHE_FULL * st["cache_capacity"]))
@@ -745,7 +847,9 @@ def main():
         if done or pre >= MAX_PREROLL:
             break
 
+    eng.selfplay_drain()  # (the last untimed move's games: not the window's)
     check_device(eng, "the untimed moves")
+    untimed_s = time.perf_counter() - t_untimed
     # ---- timed window: K steps, each drained to the host
     window = WindowGames()
     if world > 1:
@@ -805,37 +909,44 @@ def main():
                              f"of the sizes, then each rank sends its blob to rank 0 only (point-to-point "
                              f"over {args.dist_backend}) after the timed window (distributed.gather_games)"}
 
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, window.drained())
+
+    # ---- what follows runs only with --full: the headline does not need it
     # ---- tree kernels (select + expand: latency/HBM-bound) timed with HIP
     # events in a short window of their own (4 more events per simulation),
     # priced with SURVEY.md 8d's algorithmic bytes per simulation
-    eng.timer(True, tree=True)
-    sa = eng.stats()
-    for _ in range(tree_steps):
-        step_and_drain(eng)
-    sb = eng.stats()
-    eng.timer(False)
-    sims_t = max(sb["simulations"] - sa["simulations"], 1)
-    depth = (sb["path_edges"] - sa["path_edges"]) / sims_t
-    f_exp = (sb["expansions"] - sa["expansions"]) / sims_t
-    bytes_per_sim = 16 * A * depth + 24 * depth + f_exp * (16 * A + 672 + 672 + 64)
-    tree_gbs = bytes_per_sim * sims_t / (sb["tree_ms"] * 1e-3) / 1e9 if sb["tree_ms"] else 0.0
-    roofline_tree = {
-        "kernels": "select_group_kernel + expand_kernel (PUCT descent, backup, prior normalisation; the expand launch also carries the cache inserts)",
-        "bound": "hbm", "achieved": round(tree_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-        "frac": round(tree_gbs / HBM_PEAK_GBS, 5), "traffic": None,
-        "bytes_per_simulation": round(bytes_per_sim, 1), "mean_depth": round(depth, 3),
-        "expand_fraction": round(f_exp, 4),
-        "avg_launch_ms": round(sb["tree_ms"] / max(sb["tree_launches"], 1), 4),
-        "simulations_per_launch": round(sims_t / max(sb["tree_launches"] / 2, 1), 1),
-        "basis": "16*A*d + 24*d + f_exp*(16*A + 672 + 672 + 64) bytes per simulation (SURVEY.md 8d) x "
-                 "simulations / summed select+expand event time; latency-bound (dependent loads down "
-                 "each path), not bandwidth-bound",
-    }
+    roofline_tree = None
+    if args.full:
+        eng.timer(True, tree=True)
+        sa = eng.stats()
+        for _ in range(tree_steps):
+            step_and_drain(eng)
+        sb = eng.stats()
+        eng.timer(False)
+        sims_t = max(sb["simulations"] - sa["simulations"], 1)
+        depth = (sb["path_edges"] - sa["path_edges"]) / sims_t
+        f_exp = (sb["expansions"] - sa["expansions"]) / sims_t
+        bytes_per_sim = 16 * A * depth + 24 * depth + f_exp * (16 * A + 672 + 672 + 64)
+        tree_gbs = bytes_per_sim * sims_t / (sb["tree_ms"] * 1e-3) / 1e9 if sb["tree_ms"] else 0.0
+        roofline_tree = {
+            "kernels": "select_group_kernel + expand_kernel (PUCT descent, backup, prior normalisation; the expand launch also carries the cache inserts)",
+            "bound": "hbm", "achieved": round(tree_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": round(tree_gbs / HBM_PEAK_GBS, 5), "traffic": None,
+            "bytes_per_simulation": round(bytes_per_sim, 1), "mean_depth": round(depth, 3),
+            "expand_fraction": round(f_exp, 4),
+            "avg_launch_ms": round(sb["tree_ms"] / max(sb["tree_launches"], 1), 4),
+            "simulations_per_launch": round(sims_t / max(sb["tree_launches"] / 2, 1), 1),
+            "basis": "16*A*d + 24*d + f_exp*(16*A + 672 + 672 + 64) bytes per simulation (SURVEY.md 8d) x "
+                     "simulations / summed select+expand event time; latency-bound (dependent loads down "
+                     "each path), not bandwidth-bound",
+        }
 
     # ---- second window, same slots continuing, cache bypassed: the rate
     # without the reference's plays_inferences semantics (every leaf evaluated)
     off = None
-    if args.cache_log2 and not args.no_cache_window:
+    if args.full and args.cache_log2 and not args.no_cache_window:
         eng.cache_enable(False)
         if world > 1:
             dist.barrier()
@@ -901,7 +1012,7 @@ def main():
 
     # the same kernels alone on one stream at the live per-lane batch (what a
     # launch costs without the other lane's kernels sharing the CUs)
-    if rank == 0:
+    if args.full and rank == 0:
         nb = max(1, int(round(boards_per_launch)))
         rng = np.random.RandomState(1)
         bx = rng.randint(-1, 2, (nb, args.height, args.width))
@@ -949,10 +1060,15 @@ def main():
                 "global_batch": args.slots * world,
                 "parallelism": f"games sharded over {world} GPU(s)",
             },
+            "full": bool(args.full),
+            "dump_outputs": dumped,
             "lanes": eng.lanes,
             "hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4")),
             "untimed_moves": pre,
-            "untimed_rule": (f"max(--warmup, {MIN_PREROLL}) moves and until the transposition cache is "
+            "untimed_seconds": round(untimed_s, 2),
+            "setup_seconds": round(t_untimed - t_start, 2),
+            "untimed_rule": (f"max(--warmup, {MIN_PREROLL}, {UNTIMED_PER_TURNOVER} x cache capacity / (slots x sims)) "
+                             f"moves, then {UNTIMED_BLOCK} at a time until the transposition cache is "
                              f"{CACHE_FULL:.0%} full and has taken {CACHE_TURNOVER}x its capacity in inserts "
                              f"(LRU content turned over: stationary hit rate, profiles/r6/cache_curve*)"),
             "games_timed": int(drained_all),

@@ -5,7 +5,7 @@ set -e
 OUT=gpurun_out/ab_lanes
 mkdir -p $OUT
 for l in 2 3; do
-  timeout -k 10 300 python3 bench.py --lanes $l --steps 20 --warmup 40 --no-cpu-baseline --no-cache-window > $OUT/c4_l$l.json 2> $OUT/c4_l$l.err
+  timeout -k 10 300 python3 bench.py --full --lanes $l --steps 20 --warmup 40 --no-cpu-baseline --no-cache-window > $OUT/c4_l$l.json 2> $OUT/c4_l$l.err
 done
 for l in 1 2; do
   timeout -k 10 300 python3 bench.py --game chess --lanes $l --no-cpu-baseline > $OUT/chess_l$l.json 2> $OUT/chess_l$l.err

@@ -7,8 +7,8 @@ R=$PWD
 OUT=$R/gpurun_out/final
 mkdir -p $OUT
 export TMPDIR=/tmp
-timeout -k 10 400 python3 bench.py > $OUT/bench_c4.json 2> $OUT/bench_c4.err
-timeout -k 10 400 python3 bench.py --game chess > $OUT/bench_chess.json 2> $OUT/bench_chess.err
+timeout -k 10 400 python3 bench.py --full > $OUT/bench_c4.json 2> $OUT/bench_c4.err
+timeout -k 10 400 python3 bench.py --full --game chess > $OUT/bench_chess.json 2> $OUT/bench_chess.err
 bash profiles/collect_r1.sh > $OUT/collect_r1.log 2>&1
 (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/chess_trace -o run --output-format csv -- \
   python3 $R/bench.py --game chess --warmup 1 --steps 1 --no-cpu-baseline > $OUT/chess_trace.json 2> $OUT/chess_trace.err)

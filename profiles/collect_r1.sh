@@ -11,7 +11,7 @@ OUT=$R/gpurun_out/prof_r1
 mkdir -p $OUT
 export TMPDIR=/tmp
 (cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- \
-  python3 $R/bench.py --steps 5 --warmup 20 --no-cpu-baseline --no-cache-window > $OUT/bench_trace.json 2> $OUT/bench_trace.err)
+  python3 $R/bench.py --full --steps 5 --warmup 20 --no-cpu-baseline --no-cache-window > $OUT/bench_trace.json 2> $OUT/bench_trace.err)
 bash profiles/pmc_traffic.sh 4096 > $OUT/pmc_traffic.log 2>&1
 bash profiles/pmc_conv.sh 4096 0 > $OUT/pmc_conv.log 2>&1
 python3 profiles/summarize.py $OUT > $OUT/summary.md

@@ -13,7 +13,7 @@ OUT=$R/gpurun_out/prof_r2
 mkdir -p $OUT
 export TMPDIR=/tmp
 (cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- \
-  python3 $R/bench.py --steps 10 --no-cpu-baseline --no-cache-window > $OUT/bench_trace.json 2> $OUT/bench_trace.err)
+  python3 $R/bench.py --full --steps 10 --no-cpu-baseline --no-cache-window > $OUT/bench_trace.json 2> $OUT/bench_trace.err)
 bash profiles/pmc_traffic.sh 4096 r2 > $OUT/pmc_traffic.log 2>&1
 cp $R/gpurun_out/pmc_traffic/pmc_conv_traffic.json $OUT/
 mv $R/gpurun_out/pmc_traffic $OUT/

@@ -3,13 +3,13 @@
 # Usage (GPU box): bash profiles/gpu_check.sh <tag>
 set -o pipefail
 tag=${1:-r2}
-out=gpurun_out/$tag
+out=${OUT_ROOT:-bench_out}/$tag
 mkdir -p "$out"
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread \
     > "$out/gpu_tests.log" 2>&1 || { tail -30 "$out/gpu_tests.log"; exit 1; }
 tail -3 "$out/gpu_tests.log"
-timeout -k 10 300 python bench.py > "$out/bench_w5.json" 2> "$out/bench_w5.err" || { cat "$out/bench_w5.err"; exit 1; }
-timeout -k 10 300 python bench.py --warmup 60 --no-cpu-baseline > "$out/bench_w60.json" 2> "$out/bench_w60.err" \
+timeout -k 10 300 python bench.py --full > "$out/bench_w5.json" 2> "$out/bench_w5.err" || { cat "$out/bench_w5.err"; exit 1; }
+timeout -k 10 300 python bench.py --full --warmup 60 --no-cpu-baseline > "$out/bench_w60.json" 2> "$out/bench_w60.err" \
     || { cat "$out/bench_w60.err"; exit 1; }
 python - "$out" <<'EOF'
 import json, sys

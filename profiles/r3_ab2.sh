@@ -14,7 +14,7 @@ done
 i=0
 for p in 1 0 1 0; do
   i=$((i+1))
-  AZ_TOWER_PLAN=$p timeout -k 10 300 python bench.py --no-cpu-baseline --no-cache-window > $out/b${p}_$i.json 2> $out/b${p}_$i.err || { tail -5 $out/b${p}_$i.err; exit 1; }
+  AZ_TOWER_PLAN=$p timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-cache-window > $out/b${p}_$i.json 2> $out/b${p}_$i.err || { tail -5 $out/b${p}_$i.err; exit 1; }
   python3 -c "
 import json,sys; d=json.loads(open('$out/b${p}_$i.json').read().strip().splitlines()[-1]); r=d['roofline']
 print('plan $p', d['value'], d['ms_per_step'], 'tower', r['avg_launch_ms'], 'boards', r['boards_per_launch'], 'frac', r['frac'], 'iso', r['isolated']['avg_launch_ms'], 'busy_union', r['busy_union']['frac'], 'hit', d['transposition_cache']['hit_rate'])" | tee -a $out/bench.txt

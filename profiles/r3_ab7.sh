@@ -12,7 +12,7 @@ i=0
 for v in base gb256 gb1024 base gb256 gb1024; do
   i=$((i+1))
   if [ $v = base ]; then lib=custom-alphazero_amd/custom_alphazero/_lib/libaz.so; else lib=profiles/ab_libs/$v/libaz.so; fi
-  AZ_LIB_PATH=$PWD/$lib timeout -k 10 300 python bench.py --no-cpu-baseline --no-cache-window > $out/b${v}_$i.json 2> $out/b${v}_$i.err || { tail -5 $out/b${v}_$i.err; exit 1; }
+  AZ_LIB_PATH=$PWD/$lib timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-cache-window > $out/b${v}_$i.json 2> $out/b${v}_$i.err || { tail -5 $out/b${v}_$i.err; exit 1; }
   python3 -c "
 import json,sys; d=json.loads(open('$out/b${v}_$i.json').read().strip().splitlines()[-1]); r=d['roofline']
 print('$v', d['value'], d['ms_per_step'], 'tower', r['avg_launch_ms'], 'frac', r['frac'], 'iso', r['isolated']['avg_launch_ms'], 'busy_union', r['busy_union']['frac'])" | tee -a $out/bench.txt

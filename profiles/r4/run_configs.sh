@@ -6,10 +6,10 @@ set -o pipefail
 T=${TAG:-r4}
 OUT=gpurun_out/configs_$T
 mkdir -p $OUT
-timeout -k 10 420 python3 -u bench.py > $OUT/c4.json 2> $OUT/c4.err || exit 1
-timeout -k 10 400 python3 -u bench.py --height 9 --width 9 --n 5 --sims 200 --slots 8192 --steps 10 --warmup 30 \
+timeout -k 10 420 python3 -u bench.py --full > $OUT/c4.json 2> $OUT/c4.err || exit 1
+timeout -k 10 400 python3 -u bench.py --full --height 9 --width 9 --n 5 --sims 200 --slots 8192 --steps 10 --warmup 30 \
   --no-cpu-baseline > $OUT/c5_9x9.json 2> $OUT/c5_9x9.err || exit 1
-timeout -k 10 400 python3 -u bench.py --sims 400 --slots 16384 --steps 10 --warmup 30 --no-cpu-baseline \
+timeout -k 10 400 python3 -u bench.py --full --sims 400 --slots 16384 --steps 10 --warmup 30 --no-cpu-baseline \
   > $OUT/s400_16k.json 2> $OUT/s400_16k.err || exit 1
 timeout -k 10 400 python3 -u bench.py --game chess --no-cpu-baseline > $OUT/chess.json 2> $OUT/chess.err || exit 1
 for f in $OUT/*.json; do python3 -c "

@@ -10,7 +10,7 @@ out=gpurun_out/$tag
 mkdir -p "$out"
 for q in 4 8; do
   for lanes in 2 3 4; do
-    GPU_MAX_HW_QUEUES=$q timeout -k 10 240 python bench.py --game $game --no-cpu-baseline --lanes $lanes \
+    GPU_MAX_HW_QUEUES=$q timeout -k 10 240 python bench.py --full --game $game --no-cpu-baseline --lanes $lanes \
         > "$out/${game}_q${q}_l${lanes}.json" 2> "$out/${game}_q${q}_l${lanes}.err" || { tail -5 "$out/${game}_q${q}_l${lanes}.err"; exit 1; }
     python - "$out/${game}_q${q}_l${lanes}.json" "$q" "$lanes" <<'PY'
 import json, sys

@@ -6,8 +6,8 @@
 set -o pipefail
 out=gpurun_out/r5d
 mkdir -p $out
-timeout -k 10 420 python3 -u bench.py > $out/c4.json 2> $out/c4.err || { tail -5 $out/c4.err; exit 1; }
-timeout -k 10 300 python3 -u bench.py --height 9 --width 9 --n 5 --sims 200 --slots 8192 --steps 10 --warmup 30 \
+timeout -k 10 420 python3 -u bench.py --full > $out/c4.json 2> $out/c4.err || { tail -5 $out/c4.err; exit 1; }
+timeout -k 10 300 python3 -u bench.py --full --height 9 --width 9 --n 5 --sims 200 --slots 8192 --steps 10 --warmup 30 \
   --no-cpu-baseline > $out/c5_9x9.json 2> $out/c5_9x9.err || { tail -5 $out/c5_9x9.err; exit 1; }
 timeout -k 10 300 python3 -u bench.py --game chess --no-cpu-baseline > $out/chess.json 2> $out/chess.err || { tail -5 $out/chess.err; exit 1; }
 timeout -k 10 400 python3 -u bench.py --game chess --warmup 40 --no-cpu-baseline > $out/chess_mid.json 2> $out/chess_mid.err || { tail -5 $out/chess_mid.err; exit 1; }

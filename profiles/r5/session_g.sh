@@ -16,7 +16,7 @@ R=$PWD
 export TMPDIR=/tmp
 cd /tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $R/$out/trace -o run --output-format csv -- \
-  python3 $R/bench.py --steps 10 --no-cpu-baseline --no-cache-window > $R/$out/bench_trace.json 2> $R/$out/bench_trace.err || exit 1
+  python3 $R/bench.py --full --steps 10 --no-cpu-baseline --no-cache-window > $R/$out/bench_trace.json 2> $R/$out/bench_trace.err || exit 1
 cd $R
 python3 profiles/summarize.py $out r5 > $out/summary.md 2>&1
 find $out -name "*kernel_trace.csv" -size +20M -delete

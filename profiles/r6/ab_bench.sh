@@ -11,7 +11,7 @@ for n in "${names[@]}"; do
   i=$((i+1))
   if [ "$n" == "prod" ]; then unset AZ_LIB_PATH; else export AZ_LIB_PATH=$PWD/profiles/ab_libs/$n/libaz.so; fi
   out=gpurun_out/r6/ab_$TAG/${i}_$n.json
-  timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-cache-window "$@" > $out 2> ${out%.json}.err || { echo "FAIL $n"; tail -5 ${out%.json}.err; exit 1; }
+  timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-cache-window "$@" > $out 2> ${out%.json}.err || { echo "FAIL $n"; tail -5 ${out%.json}.err; exit 1; }
   python3 - "$out" "$n" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

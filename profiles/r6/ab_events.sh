@@ -7,7 +7,7 @@ mkdir -p gpurun_out/r6/abe_$TAG
 for i in $(seq 1 $N); do
   for ev in 1 0; do
     out=gpurun_out/r6/abe_$TAG/${i}_ev$ev.json
-    AZ_BENCH_WINDOW_EVENTS=$ev timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-cache-window > $out 2> ${out%.json}.err \
+    AZ_BENCH_WINDOW_EVENTS=$ev timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-cache-window > $out 2> ${out%.json}.err \
       || { echo "FAIL ev$ev"; tail -5 ${out%.json}.err; exit 1; }
     python3 - "$out" "events=$ev" <<'PY'
 import json, sys

@@ -8,12 +8,12 @@ mkdir -p $OUT
 timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread \
   > $OUT/gpu_tests.log 2>&1 || { tail -40 $OUT/gpu_tests.log; exit 1; }
 tail -2 $OUT/gpu_tests.log
-timeout -k 10 500 python3 -u bench.py > $OUT/c4.json 2> $OUT/c4.err || { tail -20 $OUT/c4.err; exit 1; }
+timeout -k 10 500 python3 -u bench.py --full > $OUT/c4.json 2> $OUT/c4.err || { tail -20 $OUT/c4.err; exit 1; }
 tail -c 300 $OUT/c4.json; echo
 for i in 1 2; do
   for ev in 1 4; do
     o=$OUT/ev${ev}_$i.json
-    AZ_BENCH_WINDOW_EVENTS=$ev timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-cache-window > $o 2> ${o%.json}.err \
+    AZ_BENCH_WINDOW_EVENTS=$ev timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-cache-window > $o 2> ${o%.json}.err \
       || { tail -5 ${o%.json}.err; exit 1; }
     python3 -c "
 import json; d=json.loads(open('$o').read().strip().splitlines()[-1]); r=d['roofline']

@@ -13,7 +13,7 @@ if ! skip tests; then
     > $OUT/gpu_tests.log 2>&1 || { tail -40 $OUT/gpu_tests.log; exit 1; }
   tail -2 $OUT/gpu_tests.log
 fi
-timeout -k 10 500 python3 -u bench.py > $OUT/c4.json 2> $OUT/c4.err || { tail -20 $OUT/c4.err; exit 1; }
+timeout -k 10 500 python3 -u bench.py --full > $OUT/c4.json 2> $OUT/c4.err || { tail -20 $OUT/c4.err; exit 1; }
 tail -c 600 $OUT/c4.json; echo
 if ! skip pmc; then
   TAG=_$T bash profiles/r6/collect_pmc.sh > $OUT/pmc.log 2>&1 || { tail -20 $OUT/pmc.log; exit 1; }

@@ -11,7 +11,7 @@ OUT=$R/gpurun_out/r6/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- \
-  python3 $R/bench.py --no-cpu-baseline --no-cache-window "$@" > $OUT/bench_trace.json 2> $OUT/bench_trace.err || exit 1
+  python3 $R/bench.py --full --no-cpu-baseline --no-cache-window "$@" > $OUT/bench_trace.json 2> $OUT/bench_trace.err || exit 1
 cd $R
 tr=$(find $OUT/trace -name '*kernel_trace.csv' | head -1)
 python3 profiles/summarize.py $OUT r6 > $OUT/summary.md

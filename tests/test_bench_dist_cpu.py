@@ -216,3 +216,115 @@ def test_bounded_arena_is_sized_from_the_measured_high_water_mark():
     assert not r["overflow_proof"] and r["sizing"] == "bounded"
     assert r["lane_half_edges"] == 2048 * 5894 and r["high_water_fraction"] == round(2_090_000 / (2048 * 5894), 4)
     assert "measured high-water mark" in r["rule"]
+
+
+def test_dump_outputs_orders_by_game_id_and_zeroes_rows_past_the_game(tmp_path):
+    """--dump-outputs: one float .npy per drained array, rows ordered by game
+    id whatever order the drains delivered them in, rows past a game's length
+    zero; how the games were split over the window's drains changes nothing."""
+    bench = _bench()
+    a, b = _drained(0, 1, 5), _drained(0, 2, 4)
+    for d in (a, b):  # rows past the end hold whatever the buffer held
+        for g, T in enumerate(d["lengths"]):
+            d["policies"][g, T:] = 7.0
+            d["moves"][g, T:] = 3
+    w1, w2 = bench.WindowGames(), bench.WindowGames()
+    for d in (b, a):
+        w1.add(d)
+    w2.add({k: np.concatenate([a[k], b[k][:1]]) for k in a})
+    w2.add({k: v[:0] for k, v in a.items()})
+    w2.add({k: v[1:] for k, v in b.items()})
+    r1 = bench.dump_outputs(str(tmp_path / "one"), w1.drained())
+    r2 = bench.dump_outputs(str(tmp_path / "two"), w2.drained())
+    assert r1["games"] == r1["of"] == 9 and r1["arrays"] == r2["arrays"] == sorted(a)
+    ref = {k: np.concatenate([a[k], b[k]]) for k in a}
+    assert np.all(np.diff(ref["game_ids"]) > 0)
+    for k in ref:
+        x, y = np.load(tmp_path / "one" / f"{k}.npy"), np.load(tmp_path / "two" / f"{k}.npy")
+        assert x.dtype == (np.float64 if ref[k].dtype.itemsize == 8 else np.float32), k
+        assert x.tobytes() == y.tobytes() and x.shape == ref[k].shape, k
+    pol, mov = np.load(tmp_path / "one" / "policies.npy"), np.load(tmp_path / "one" / "moves.npy")
+    for g, T in enumerate(ref["lengths"]):
+        np.testing.assert_array_equal(pol[g, :T], ref["policies"][g, :T])
+        np.testing.assert_array_equal(mov[g, :T], ref["moves"][g, :T])
+        assert not pol[g, T:].any() and not mov[g, T:].any()
+    assert r1["bytes"] == sum(np.load(tmp_path / "one" / f).nbytes for f in os.listdir(tmp_path / "one"))
+
+
+def test_dump_outputs_keeps_a_seeded_sample_under_the_size_limit(tmp_path, monkeypatch):
+    """Above the limit the dump keeps a sample of the games that depends only
+    on how many there are; an empty window writes empty arrays."""
+    bench = _bench()
+    games = _drained(0, 3, 40)
+    per_game = sum(np.zeros(v.shape[1:], np.float64 if v.dtype.itemsize == 8 else np.float32).nbytes
+                   for v in games.values())
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 10 * per_game + 5)
+    shuffled = {k: v[::-1] for k, v in games.items()}
+    r1 = bench.dump_outputs(str(tmp_path / "a"), games)
+    r2 = bench.dump_outputs(str(tmp_path / "b"), shuffled)
+    assert r1["games"] == r2["games"] == 10 and r1["of"] == 40 and r1["bytes"] <= bench.DUMP_MAX_BYTES
+    ids = np.load(tmp_path / "a" / "game_ids.npy")
+    assert np.all(np.diff(ids) > 0) and set(ids) <= set(games["game_ids"])
+    for k in games:
+        assert np.load(tmp_path / "a" / f"{k}.npy").tobytes() == np.load(tmp_path / "b" / f"{k}.npy").tobytes()
+    r0 = bench.dump_outputs(str(tmp_path / "none"), {k: v[:0] for k, v in games.items()})
+    assert r0["games"] == 0 and np.load(tmp_path / "none" / "boards.npy").shape == (0, H * W, H, W)
+    assert bench.DUMP_MAX_BYTES == 10 * per_game + 5 and _bench().DUMP_MAX_BYTES == 64 << 20
+
+
+def test_dump_outputs_writes_packed_chess_positions_as_bytes(tmp_path):
+    """The chess drain's arrays: the 80-byte position records are written as
+    their bytes, rows follow the game ids, plies past a game's length are zero."""
+    from custom_alphazero.chess.kernels import MAX_MOVES, POS_DTYPE
+    bench = _bench()
+    G, P = 4, 3
+    g = dict(game_ids=np.array([3, 1, 2, 0], np.int64), lengths=np.array([3, 2, 3, 1], np.int32),
+             results=np.zeros(G, np.int32), terminations=np.zeros(G, np.int32), expansions=np.ones(G, np.int32),
+             positions=np.zeros((G, P), POS_DTYPE), moves=np.ones((G, P), np.uint16),
+             policy_n=np.full((G, P), 20, np.int32), policy_actions=np.ones((G, P, MAX_MOVES), np.int16),
+             policy_probs=np.full((G, P, MAX_MOVES), 0.5))
+    g["positions"]["turn"] = 1 + np.arange(G)[:, None]
+    r = bench.dump_outputs(str(tmp_path), g)
+    assert r["games"] == 4 and r["arrays"] == sorted(g)
+    pos = np.load(tmp_path / "positions.npy")
+    assert pos.shape == (G, P, 80) and pos.dtype == np.float32
+    turn_byte = POS_DTYPE.fields["turn"][1]
+    lengths = np.load(tmp_path / "lengths.npy").astype(int)
+    assert list(lengths) == [1, 2, 3, 3]  # game ids 0, 1, 2, 3
+    assert list(pos[:, 0, turn_byte]) == [4, 2, 3, 1]
+    probs = np.load(tmp_path / "policy_probs.npy")
+    for i, T in enumerate(lengths):
+        assert probs[i, :T].all() and not probs[i, T:].any() and not pos[i, T:].any()
+
+
+def test_untimed_moves_are_a_function_of_the_arguments():
+    """The number of untimed moves comes from the arguments alone (the timed
+    steps then start from the same position in every run): at least
+    max(--warmup, MIN_PREROLL) and, with the cache on, UNTIMED_PER_TURNOVER
+    x capacity / (slots x sims), capped at MAX_PREROLL; the cache's counters,
+    which vary from run to run, do not enter."""
+    bench = _bench()
+    args = argparse.Namespace(warmup=5, cache_log2=26, slots=4096, sims=100)
+    st = dict(cache_gen_size=1 << 22, cache_capacity=1 << 26, cache_inserts=0, cache_entries=0)
+    n = bench.untimed_moves_planned(args, st)
+    assert n == 1262 == -(-int(bench.UNTIMED_PER_TURNOVER * (1 << 26)) // (4096 * 100))
+    assert bench.untimed_moves_planned(args, dict(st, cache_inserts=3 << 26, cache_entries=1 << 26)) == n
+    # configs[1]'s rule (CACHE_FULL, CACHE_TURNOVER) first held at move 1234-1235: inside the plan
+    assert 1235 < n < 1300
+    assert bench.untimed_moves_planned(argparse.Namespace(**dict(vars(args), warmup=2000)), st) == 2000
+    assert bench.untimed_moves_planned(argparse.Namespace(**dict(vars(args), cache_log2=0)), st) == bench.MIN_PREROLL
+    assert bench.untimed_moves_planned(args, dict(st, cache_gen_size=0)) == bench.MIN_PREROLL  # a table that only fills
+    small = argparse.Namespace(warmup=60, cache_log2=14, slots=256, sims=16)
+    assert bench.untimed_moves_planned(small, dict(st, cache_capacity=1 << 14)) == 60
+    assert bench.untimed_moves_planned(argparse.Namespace(**dict(vars(args), slots=8, sims=16)), st) == bench.MAX_PREROLL
+
+
+def test_plain_run_options(monkeypatch):
+    """--full is off by default; --dump-outputs takes the directory."""
+    bench = _bench()
+    monkeypatch.setattr(bench.sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr(bench.sys, "argv", ["bench.py", "--full", "--dump-outputs", "somewhere"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "somewhere" and a.steps == 30
