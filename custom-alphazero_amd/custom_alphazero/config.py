@@ -71,12 +71,19 @@ class ConfigModel:
     l2_penalization_term = 1e-4
     depth = 4
     maximum_learning_rate = 1e-2
+    # the schedule train() applies after every call: the rate of the range holding
+    # model.steps, else minimum_learning_rate (config.py:65-69)
+    learning_rates = {
+        range(0, 150000): 1e-2,
+        range(150000, 300000): 1e-3,
+    }
     minimum_learning_rate = 1e-4
     momentum = 0.9
     filters = 128
     # additions: Keras defaults the reference relies on implicitly
     value_hidden = 256            # ValueHead hidden_dim (model/tensorflow/model.py:110)
     bn_epsilon = 1e-3             # tf.keras BatchNormalization default
+    bn_momentum = 0.99            # tf.keras BatchNormalization default (moving statistics, training)
     forward_batch = 1024          # az_forward chunk (device buffer rows)
 
 
@@ -84,6 +91,13 @@ class ConfigServing:
     evaluation_games_number = 150   # config.py:89
     replace_min_score = 0.55        # config.py:90
     evaluate_with_mcts = False      # config.py:92
+    evaluate_with_solver = False    # config.py:93 (the solver binary is not part of this package)
+    # the training loop (train.py, model/tensorflow/train.py)
+    minimum_training_size = 2500    # config.py:83
+    samples_queue_size = 10000      # config.py:84: the replay window
+    model_evaluation_frequency = 50 # config.py:87
+    model_checkpoint_frequency = 50 # config.py:88
+    training_loop_sleep_time = 0.5  # config.py:91
 
 
 class ConfigPath:
@@ -91,6 +105,7 @@ class ConfigPath:
     self_play_dir = "self_play"
     training_dir = "training"
     evaluation_dir = "evaluation"
+    tensorboard_dir = "tensorboard"   # holds scalars.jsonl here (no TensorBoard writer)
     samples_file = "samples.npz"
     model_prefix = "model"
     model_meta = "meta.json"

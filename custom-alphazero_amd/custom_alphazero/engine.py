@@ -100,6 +100,8 @@ EXPORTED = (
     "az_selfplay_run", "az_selfplay_results", "az_selfplay_drain", "az_tree_reset", "az_tree_release", "az_tree_search", "az_tree_search_noise", "az_tree_play",
     "az_tree_info", "az_tree_export", "az_stats_get", "az_timer_enable", "az_pow_table",
     "az_cache_clear", "az_cache_enable", "az_engine_set_evaluator",
+    "az_trainer_create", "az_trainer_destroy", "az_trainer_set_weights", "az_trainer_reset_momentum",
+    "az_trainer_read", "az_trainer_step",
     # include/az_chess.h
     "az_chess_all_moves", "az_chess_legal", "az_chess_encode", "az_chess_play", "az_chess_perft",
     "az_chess_engine_create", "az_chess_engine_destroy", "az_chess_engine_set_weights",
@@ -160,6 +162,14 @@ def load_library():
         "az_cache_clear": (ctypes.c_int, [P]),
         "az_cache_enable": (ctypes.c_int, [P, ctypes.c_int]),
         "az_engine_set_evaluator": (ctypes.c_int, [P, EVAL_FN, P]),
+        "az_trainer_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(Config), ctypes.c_int,
+                                             ctypes.POINTER(P)]),
+        "az_trainer_destroy": (ctypes.c_int, [P]),
+        "az_trainer_set_weights": (ctypes.c_int, [P, ctypes.POINTER(Tensor), ctypes.c_int]),
+        "az_trainer_reset_momentum": (ctypes.c_int, [P]),
+        "az_trainer_read": (ctypes.c_int, [P, ctypes.c_int, ctypes.c_char_p, P, I64]),
+        "az_trainer_step": (ctypes.c_int, [P, P, P, P, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                           ctypes.c_double, ctypes.c_double, P]),
         "az_chess_all_moves": (ctypes.c_int, [P, ctypes.c_int]),
         "az_chess_legal": (ctypes.c_int, [ctypes.c_int, P, ctypes.c_int, P, P, P, P]),
         "az_chess_encode": (ctypes.c_int, [ctypes.c_int, P, P, ctypes.c_int, P]),
@@ -495,6 +505,79 @@ class Engine:
         out = np.zeros(int(n), np.float64)
         _check(self._L.az_pow_table(self._h, _ptr(out), int(n)))
         return out
+
+
+TRAIN_WEIGHT, TRAIN_GRAD, TRAIN_MOMENTUM = 0, 1, 2  # include/az.h AZ_TRAIN_*
+
+
+class Trainer:
+    """One libaz trainer (az_trainer_*, csrc/az_train.hip): the training step
+    of the Connect-N policy/value network -- forward with batch statistics,
+    backward, SGD with momentum -- on one device and a stream of its own.  It
+    owns its weights, gradients and momentum; tensors go in and out by their
+    weights.weight_spec names in Keras layout."""
+
+    def __init__(self, height=6, width=7, gravity=True, max_batch=256, filters=128, depth=4,
+                 value_hidden=256, bn_epsilon=1e-3, device=0):
+        from custom_alphazero.model.weights import weight_spec
+        L = load_library()
+        self.height, self.width, self.gravity = int(height), int(width), bool(gravity)
+        self.action_space = self.width if self.gravity else self.width * self.height
+        self.max_batch = int(max_batch)
+        self.spec = weight_spec(self.height, self.width, self.action_space, filters, max(int(depth), 0),
+                                value_hidden, 4)
+        cfg = Config(board_height=self.height, board_width=self.width, n=min(4, self.height, self.width),
+                     gravity=int(self.gravity), filters=filters, depth=depth, value_hidden=value_hidden,
+                     bn_epsilon=bn_epsilon)
+        handle = ctypes.c_void_p()
+        _check(L.az_trainer_create(int(device), ctypes.byref(cfg), self.max_batch, ctypes.byref(handle)))
+        self._h = handle
+        self._L = L
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.az_trainer_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # pragma: no cover - interpreter teardown
+            pass
+
+    def set_weights(self, named):
+        """named: iterable of (name, array-like or torch tensor), every tensor
+        of the spec.  Momentum is left as it is (zero at creation)."""
+        arr, n, _keep = tensor_array(named)
+        _check(self._L.az_trainer_set_weights(self._h, arr, n))
+
+    def reset_momentum(self):
+        _check(self._L.az_trainer_reset_momentum(self._h))
+
+    def read(self, name, what=TRAIN_WEIGHT):
+        """One tensor (Keras layout) as a float32 numpy array: the weight, or
+        the last step's gradient of the total loss, or the momentum buffer."""
+        shape = dict(self.spec).get(name)
+        out = np.zeros(shape if shape is not None else (1,), np.float32)
+        _check(self._L.az_trainer_read(self._h, int(what), name.encode(), _ptr(out), out.size))
+        return out
+
+    def read_all(self, what=TRAIN_WEIGHT):
+        names = [n for n, _ in self.spec
+                 if what == TRAIN_WEIGHT or n.rsplit(".", 1)[1] not in ("mean", "var")]
+        return {n: self.read(n, what) for n in names}
+
+    def step(self, x, pi, z, lr, momentum=0.9, l2=1e-4, bn_momentum=0.99):
+        """One SGD step on the batch x [n, H, W, 4], pi [n, A], z [n]; returns
+        (total, policy, value) losses of the weights before the update."""
+        x = np.ascontiguousarray(x, np.float32).reshape(-1, self.height, self.width, 4)
+        n = len(x)
+        pi = np.ascontiguousarray(pi, np.float32).reshape(n, self.action_space)
+        z = np.ascontiguousarray(z, np.float32).reshape(n)
+        losses = np.zeros(3, np.float32)
+        _check(self._L.az_trainer_step(self._h, _ptr(x), _ptr(pi), _ptr(z), n, float(lr), float(momentum),
+                                       float(l2), float(bn_momentum), _ptr(losses)))
+        return float(losses[0]), float(losses[1]), float(losses[2])
 
 
 class ChessEngine:

@@ -6,6 +6,13 @@ layout, names from model/weights.py); the forward runs in libaz
 (az_forward: the conv16 tower + heads, csrc/az_nn.hip, az_conv16.hip).  Calling the
 model returns (probabilities [B, A], value [B, 1]) as torch CPU tensors, so
 the reference's `.numpy()` idiom (mcts.py:134-137) works unchanged.
+
+Training (model.fit on one batch, model/tensorflow/train.py:24-31) is
+train_on_batch: a lazily created engine.Trainer (az_trainer_*,
+csrc/az_train.hip) that keeps the weights, gradients and SGD momentum on the
+device.  After a step the trainer's weights are the model's: get_weights(),
+hash, the inference call and save_with_meta all see them.  Momentum lives as
+long as the trainer and is not written to a checkpoint.
 """
 import json
 import os
@@ -17,6 +24,10 @@ from custom_alphazero.config import ConfigConnectN, ConfigModel, ConfigPath
 from custom_alphazero.model.tf_checkpoint import load_keras_weights, save_keras_weights
 from custom_alphazero.model.weights import (content_hash, init_weights, keras_order, reference_hash,
                                             weight_spec)
+
+
+def _np(a):
+    return a.numpy() if hasattr(a, "numpy") else np.asarray(a)
 
 
 class PolicyValueModel:
@@ -39,6 +50,9 @@ class PolicyValueModel:
         self._engine = None
         self._engine_version = -1
         self._version = 0
+        self._trainer = None
+        self._trainer_version = -1   # the _version whose weights the trainer holds
+        self._trainer_ahead = False  # the trainer stepped: self.weights are stale until _pull()
         # the reference's constructor runs a dummy forward on
         # np.random.rand(1, *input_dim) (model/tensorflow/model.py:167-169):
         # the same draws from numpy's global stream, so a caller seeding
@@ -48,7 +62,16 @@ class PolicyValueModel:
 
     # ------------------------------------------------------------ weights
     def engine_weights(self):
+        self._pull()
         return [(name, self.weights[name]) for name, _ in self.spec]
+
+    def _pull(self):
+        """After training steps: the trainer's weights and moving statistics become self.weights."""
+        if self._trainer_ahead:
+            import torch
+            for name, w in self._trainer.read_all().items():
+                self.weights[name] = torch.from_numpy(w).to(self.device)
+            self._trainer_ahead = False
 
     @property
     def weight_names(self):
@@ -58,6 +81,7 @@ class PolicyValueModel:
 
     def get_weights(self):
         shapes = dict(self.spec)
+        self._pull()
         return [self.weights[n].detach().cpu().numpy().reshape(shapes[n]) for n in self.weight_names]
 
     def set_weights(self, arrays):
@@ -66,12 +90,18 @@ class PolicyValueModel:
         if len(arrays) != len(self.spec):
             raise ValueError(f"expected {len(self.spec)} arrays, got {len(arrays)}")
         shapes = dict(self.spec)
+        new = {}
         for name, a in zip(self.weight_names, arrays):
             a = np.asarray(a, np.float32)
             if a.shape != tuple(shapes[name]):
                 raise ValueError(f"{name}: shape {a.shape} != {shapes[name]}")
-            self.weights[name] = torch.from_numpy(a.copy()).to(self.device)
+            new[name] = torch.from_numpy(a.copy()).to(self.device)
+        self.weights.update(new)
+        self._trainer_ahead = False  # every tensor was replaced
         self._version += 1
+        if self._trainer is not None:  # an existing trainer follows the model (its momentum stays)
+            self._trainer.set_weights(self.engine_weights())
+            self._trainer_version = self._version
 
     @property
     def hash(self) -> int:
@@ -119,6 +149,38 @@ class PolicyValueModel:
         return torch.from_numpy(probs), torch.from_numpy(values.reshape(-1, 1))
 
     call = __call__
+
+    # ------------------------------------------------------------ training
+    def trainer(self):
+        """The model's engine.Trainer (created on first use, max_batch =
+        ConfigModel.batch_size), holding the model's current weights."""
+        if self._trainer is None:
+            H, W, C = self.input_dim
+            if C != 4 or self.action_space not in (W, H * W):
+                # chess (118 planes, 1880 actions) is out of the trainer's scope: AZ_E_INVALID
+                raise az.AzError("libaz error -1: the trainer implements the Connect-N network only "
+                                 f"(input planes {C}, action space {self.action_space})")
+            self._trainer = az.Trainer(H, W, gravity=self.action_space == W, max_batch=ConfigModel.batch_size,
+                                       filters=ConfigModel.filters, depth=self.depth,
+                                       value_hidden=ConfigModel.value_hidden,
+                                       bn_epsilon=ConfigModel.bn_epsilon, device=self.device.index or 0)
+        if self._trainer_version != self._version:
+            self._trainer.set_weights(self.engine_weights())
+            self._trainer_version = self._version
+        return self._trainer
+
+    def train_on_batch(self, inputs, policy_labels, value_labels):
+        """One SGD step (Keras SGD with ConfigModel.momentum at the model's
+        learning rate, l2_penalization_term on every kernel) on one batch;
+        returns the total loss before the update, as Keras reports a batch."""
+        x = np.asarray(_np(inputs), np.float32).reshape((-1,) + self.input_dim)
+        tr = self.trainer()
+        total, _, _ = tr.step(x, _np(policy_labels), _np(value_labels), self.learning_rate,
+                              ConfigModel.momentum, ConfigModel.l2_penalization_term, ConfigModel.bn_momentum)
+        self._version += 1
+        self._trainer_version = self._version
+        self._trainer_ahead = True
+        return total
 
     # ------------------------------------------------------------ persistence
     def save_with_meta(self, path):

@@ -282,6 +282,31 @@ int az_timer_enable(az_engine* eng, int on);
 /* The host-built libm pow(k, 0.5) table the kernels use (tests). */
 int az_pow_table(az_engine* eng, double* out, int64_t n);
 
+/* The training step (model/tensorflow/train.py:14-116: model.fit on one
+ * batch): forward with batch statistics in every BatchNormalization, the
+ * reference's loss (base_layers.py:12-17) plus l2 * sum ||kernel||^2, the
+ * backward pass and Keras SGD with momentum, all fp32 on the device
+ * (csrc/az_train.hip; DESIGN.md "Trainer").  Connect-N only: 4 input planes,
+ * filters = 128, depth 1..16.  A trainer owns its weights, gradients and
+ * momentum and runs on a stream of its own; every call is synchronous.  Two
+ * steps from the same state and batch give bitwise equal results. */
+typedef struct az_trainer az_trainer;
+#define AZ_TRAIN_WEIGHT 0
+#define AZ_TRAIN_GRAD 1       /* d(total loss)/d(tensor) of the last step */
+#define AZ_TRAIN_MOMENTUM 2
+/* cfg: board_height/width, gravity, filters, depth, value_hidden, bn_epsilon; the rest is ignored */
+int az_trainer_create(int device, const az_config* cfg, int max_batch, az_trainer** out);
+int az_trainer_destroy(az_trainer* tr);
+/* Keras-layout tensors (weights.py names), all of them; momentum is left as it is (zero at create) */
+int az_trainer_set_weights(az_trainer* tr, const az_tensor* tensors, int n);
+int az_trainer_reset_momentum(az_trainer* tr);
+/* one tensor by name into a host buffer (Keras layout); mean/var only as AZ_TRAIN_WEIGHT */
+int az_trainer_read(az_trainer* tr, int what, const char* name, float* out, int64_t numel);
+/* x [n][H][W][4], pi [n][A], z [n] f32 host; 2 <= n <= max_batch; losses[3] = total, policy, value
+ * (of the weights before the update).  AZ_E_STATE before az_trainer_set_weights. */
+int az_trainer_step(az_trainer* tr, const float* x, const float* pi, const float* z, int n,
+                    double lr, double momentum, double l2, double bn_momentum, float* losses);
+
 #ifdef __cplusplus
 }
 #endif
