@@ -898,14 +898,14 @@ int az_trainer_create(int device, const az_config* cfg, int max_batch, az_traine
   if (!cfg || !out) return fail_abi(AZ_E_INVALID, "az_trainer_create: null argument");
   const az_config& c = *cfg;
   if (c.board_height < 2 || c.board_width < 2 || c.board_height * c.board_width > T::kMaxCellsTrain)
-    return fail_abi(AZ_E_INVALID, "az_trainer_create: board must be 2..128 cells");
+    return fail_abi(AZ_E_INVALID, "az_trainer_create: board must be at least 2x2 and at most 128 cells");
   if (c.filters != T::kF) return fail_abi(AZ_E_INVALID, "az_trainer_create: only filters = 128 is implemented");
   if (c.depth < 1 || c.depth > 16) return fail_abi(AZ_E_INVALID, "az_trainer_create: depth must be 1..16");
   if (c.value_hidden < 1 || c.value_hidden > T::kMaxHidden)
     return fail_abi(AZ_E_INVALID, "az_trainer_create: value_hidden must be 1..1024");
   if (!(c.bn_epsilon > 0)) return fail_abi(AZ_E_INVALID, "az_trainer_create: bn_epsilon must be positive");
-  if (max_batch < 2 || (int64_t)max_batch * c.board_height * c.board_width * T::kF >= (1ll << 31))
-    return fail_abi(AZ_E_INVALID, "az_trainer_create: max_batch must be >= 2 and max_batch*H*W*128 < 2^31");
+  if (max_batch < 1 || (int64_t)max_batch * c.board_height * c.board_width * T::kF >= (1ll << 31))
+    return fail_abi(AZ_E_INVALID, "az_trainer_create: max_batch must be >= 1 and max_batch*H*W*128 < 2^31");
   if (device < 0) return fail_abi(AZ_E_INVALID, "az_trainer_create: bad device ordinal");
   int count = 0;
   if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
@@ -991,8 +991,8 @@ int az_trainer_read(az_trainer* tr, int what, const char* name, float* out, int6
 int az_trainer_step(az_trainer* tr, const float* x, const float* pi, const float* z, int n, double lr,
                     double momentum, double l2, double bn_momentum, float* losses) {
   if (!tr || !x || !pi || !z) return fail_abi(AZ_E_INVALID, "az_trainer_step: null argument");
-  if (n < 2 || n > tr->max_batch)
-    return fail_abi(AZ_E_INVALID, "az_trainer_step: n must be 2..max_batch (batch statistics need two samples)");
+  // one board is a batch: every BatchNormalization takes its statistics over the n*H*W rows
+  if (n < 1 || n > tr->max_batch) return fail_abi(AZ_E_INVALID, "az_trainer_step: n must be 1..max_batch");
   if (!tr->has_weights) return fail_abi(AZ_E_STATE, "az_trainer_step: no weights (az_trainer_set_weights first)");
   AZT_HIP(hipSetDevice(tr->device));
   hipStream_t s = tr->stream;

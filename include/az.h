@@ -294,7 +294,8 @@ typedef struct az_trainer az_trainer;
 #define AZ_TRAIN_WEIGHT 0
 #define AZ_TRAIN_GRAD 1       /* d(total loss)/d(tensor) of the last step */
 #define AZ_TRAIN_MOMENTUM 2
-/* cfg: board_height/width, gravity, filters, depth, value_hidden, bn_epsilon; the rest is ignored */
+/* cfg: board_height/width (each >= 2, at most 128 cells), gravity, filters (128), depth (1..16),
+ * value_hidden (1..1024), bn_epsilon; the rest is ignored.  max_batch >= 1, max_batch*H*W*128 < 2^31. */
 int az_trainer_create(int device, const az_config* cfg, int max_batch, az_trainer** out);
 int az_trainer_destroy(az_trainer* tr);
 /* Keras-layout tensors (weights.py names), all of them; momentum is left as it is (zero at create) */
@@ -302,8 +303,9 @@ int az_trainer_set_weights(az_trainer* tr, const az_tensor* tensors, int n);
 int az_trainer_reset_momentum(az_trainer* tr);
 /* one tensor by name into a host buffer (Keras layout); mean/var only as AZ_TRAIN_WEIGHT */
 int az_trainer_read(az_trainer* tr, int what, const char* name, float* out, int64_t numel);
-/* x [n][H][W][4], pi [n][A], z [n] f32 host; 2 <= n <= max_batch; losses[3] = total, policy, value
- * (of the weights before the update).  AZ_E_STATE before az_trainer_set_weights. */
+/* x [n][H][W][4], pi [n][A], z [n] f32 host; 1 <= n <= max_batch (one board is a batch: the batch
+ * statistics run over its n*H*W rows); losses[3] = total, policy, value (of the weights before the
+ * update).  AZ_E_STATE before az_trainer_set_weights. */
 int az_trainer_step(az_trainer* tr, const float* x, const float* pi, const float* z, int n,
                     double lr, double momentum, double l2, double bn_momentum, float* losses);
 

@@ -248,8 +248,8 @@ def test_argument_errors():
     with pytest.raises(az.AzError, match="error -3"):  # AZ_E_STATE: a step before set_weights
         tr.step(x[:4], pi[:4], z[:4], 1e-2)
     tr.set_weights(weights.items())
-    with pytest.raises(az.AzError, match="error -1"):  # n = 1
-        tr.step(x[:1], pi[:1], z[:1], 1e-2)
+    with pytest.raises(az.AzError, match="error -1"):  # n = 0
+        tr.step(x[:0], pi[:0], z[:0], 1e-2)
     with pytest.raises(az.AzError, match="error -1"):  # n > max_batch
         tr.step(x, pi, z, 1e-2)
     with pytest.raises(az.AzError, match="error -1.*unknown tensor"):
@@ -266,6 +266,18 @@ def test_argument_errors():
         az.Trainer(6, 7, True, max_batch=4, filters=64, depth=1)
     with pytest.raises(az.AzError, match="error -1.*depth"):
         az.Trainer(6, 7, True, max_batch=4, depth=17)
+    # the refusals that guard heads_kernel's LDS arrays and the 32-bit row indices (host side, nothing is launched)
+    with pytest.raises(az.AzError, match="error -1.*cells"):
+        az.Trainer(12, 12, True, max_batch=4, depth=1)  # 144 cells
+    with pytest.raises(az.AzError, match="error -1.*value_hidden"):
+        az.Trainer(6, 7, True, max_batch=4, depth=1, value_hidden=1025)
+    with pytest.raises(az.AzError, match="error -1.*value_hidden"):
+        az.Trainer(6, 7, True, max_batch=4, depth=1, value_hidden=0)
+    with pytest.raises(az.AzError, match="error -1.*depth"):
+        az.Trainer(6, 7, True, max_batch=4, depth=0)
+    assert 399458 * 6 * 7 * 128 >= 2 ** 31 > 399457 * 6 * 7 * 128
+    with pytest.raises(az.AzError, match="error -1.*max_batch"):
+        az.Trainer(6, 7, True, max_batch=399458, depth=1)  # the first max_batch * H * W * 128 >= 2^31
     # chess (118 planes, 1880 actions) is refused
     from custom_alphazero.model.policy_value import PolicyValueModel
     chess = PolicyValueModel.__new__(PolicyValueModel)

@@ -158,7 +158,8 @@ def conv_bias_unit(name):
 # 4.5 million ReLU inputs, so some input always lies within about 1e-6 of zero;
 # the widest margin leaves the least room for a flip under another rounding.
 BATCH_SEEDS = {(6, 7, True, 3, 1): 2, (5, 5, False, 5, 2): 36, (6, 7, True, 37, 2): 22,
-               (6, 7, True, 64, 4): 4, (6, 7, True, 10, 4): 31}
+               (6, 7, True, 64, 4): 4, (6, 7, True, 10, 4): 31,
+               (6, 7, True, 9, 4): 1}  # train() on 4, 4 and 1 samples: margin 1.0e-5 over the three steps
 MIN_RELU_MARGIN = 1e-6  # some twenty float32 roundings of an O(1) BatchNormalization output
 
 CLEAR_MARGIN = 2e-5  # some 300 float32 roundings of an O(1) value: ten times either fp32 run's error there
@@ -202,19 +203,28 @@ def clear_kinks(weights, x, depth, margin=CLEAR_MARGIN, eps=1e-3):
 _CACHE = {}
 
 
-def reference_run(H, W, gravity, n, depth, steps=1, lr=1e-2, momentum=0.9, l2=1e-4, bn_momentum=0.99, seed=0):
+def reference_run(H, W, gravity, n, depth, steps=1, lr=1e-2, momentum=0.9, l2=1e-4, bn_momentum=0.99, seed=0,
+                  hidden=256, weights_mod=None, batch_mod=None):
     """Float64 and float32 CPU runs of `steps` steps on one fixed batch, computed
     once per shape and shared (callers must not modify the result).  `seed`
     draws the weights, which clear_kinks then moves clear of every ReLU kink of
-    the first step; the batch's seed is BATCH_SEEDS' for the shape.  Returns a
-    dict: spec, weights, batch, and per dtype key ('f64', 'f32') the list of
-    per-step records {losses, grad, mom, w, relu_margin}."""
-    key = (H, W, gravity, n, depth, steps, lr, momentum, l2, bn_momentum, seed)
+    the first step; the batch's seed is BATCH_SEEDS' for the shape.  `hidden`
+    is the value head's width.  `weights_mod(weights) -> weights` and
+    `batch_mod((x, pi, z)) -> (x, pi, z)` are module-level functions (they are
+    part of the cache key) that reshape the drawn inputs before clear_kinks
+    sees them.  Returns a dict: spec, weights, batch, and per dtype key ('f64',
+    'f32') the list of per-step records {losses, grad, mom, w, relu_margin}."""
+    key = (H, W, gravity, n, depth, steps, lr, momentum, l2, bn_momentum, seed, hidden, weights_mod, batch_mod)
     if key in _CACHE:
         return _CACHE[key]
-    spec = make_spec(H, W, gravity, depth)
+    spec = make_spec(H, W, gravity, depth, hidden=hidden)
     batch = make_batch(H, W, gravity, n, BATCH_SEEDS.get((H, W, gravity, n, depth), 0))
-    weights = clear_kinks(make_weights(spec, seed), batch[0], depth)
+    weights = make_weights(spec, seed)
+    if weights_mod is not None:
+        weights = weights_mod({k: np.array(v, np.float32) for k, v in weights.items()})
+    if batch_mod is not None:
+        batch = tuple(np.ascontiguousarray(a, np.float32) for a in batch_mod(tuple(a.copy() for a in batch)))
+    weights = clear_kinks(weights, batch[0], depth)
     out = {"spec": spec, "weights": weights, "batch": batch}
     for tag, dt in (("f64", torch.float64), ("f32", torch.float32)):
         ref = RefTrainer(spec, weights, depth, dt)
