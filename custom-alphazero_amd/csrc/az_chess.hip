@@ -11,10 +11,7 @@
 
 #include "../../include/az.h"
 #include "az_chess.h"
-
-namespace az {
-int fail_abi(int code, const std::string& msg);  // az_engine.hip (az_last_error)
-}
+#include "az_host.h"
 
 namespace azc {
 
@@ -91,28 +88,17 @@ struct DevCtx {
 std::mutex g_mu;
 DevCtx g_ctx[64];
 
-#define AZC_HIP(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t err__ = (expr);                                                                 \
-    if (err__ != hipSuccess)                                                                   \
-      return az::fail_abi(AZ_E_HIP, std::string(#expr) + ": " + hipGetErrorString(err__));     \
-  } while (0)
-
 int ctx_for(int device, DevCtx** out) {
   if (device < 0 || device >= 64) return az::fail_abi(AZ_E_INVALID, "chess: bad device ordinal");
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
-    return az::fail_abi(AZ_E_HIP, "chess: no HIP device visible (libaz has no CPU fallback)");
-  if (device >= count) return az::fail_abi(AZ_E_INVALID, "chess: device ordinal out of range");
-  AZC_HIP(hipSetDevice(device));
+  AZ_TRY(az::open_device(device, "chess: device ordinal out of range"));
   std::lock_guard<std::mutex> lk(g_mu);
   DevCtx& c = g_ctx[device];
   if (!c.ready) {
-    AZC_HIP(upload_rays());
-    AZC_HIP(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
+    AZ_HIP(upload_rays());
+    AZ_HIP(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
     std::vector<int16_t> lut = action_lut();
-    AZC_HIP(hipMalloc(&c.lut, lut.size() * sizeof(int16_t)));
-    AZC_HIP(hipMemcpy(c.lut, lut.data(), lut.size() * sizeof(int16_t), hipMemcpyHostToDevice));
+    AZ_HIP(hipMalloc(&c.lut, lut.size() * sizeof(int16_t)));
+    AZ_HIP(hipMemcpy(c.lut, lut.data(), lut.size() * sizeof(int16_t), hipMemcpyHostToDevice));
     c.ready = true;
   }
   *out = &c;
@@ -283,27 +269,27 @@ extern "C" int az_chess_legal(int device, const az_chess_pos* pos, int n, uint16
   DBuf<uint16_t> dmv;
   DBuf<int32_t> dcnt, dout;
   DBuf<uint8_t> dmask;
-  AZC_HIP(dpos.alloc(n));
-  AZC_HIP(dmv.alloc((size_t)n * AZ_CHESS_MAX_MOVES));
-  AZC_HIP(dcnt.alloc(n));
-  if (outcome_out) AZC_HIP(dout.alloc(n));
+  AZ_HIP(dpos.alloc(n));
+  AZ_HIP(dmv.alloc((size_t)n * AZ_CHESS_MAX_MOVES));
+  AZ_HIP(dcnt.alloc(n));
+  if (outcome_out) AZ_HIP(dout.alloc(n));
   if (mask) {
-    AZC_HIP(dmask.alloc((size_t)n * AZ_CHESS_ACTIONS));
-    AZC_HIP(hipMemsetAsync(dmask.p, 0, (size_t)n * AZ_CHESS_ACTIONS, c->stream));
+    AZ_HIP(dmask.alloc((size_t)n * AZ_CHESS_ACTIONS));
+    AZ_HIP(hipMemsetAsync(dmask.p, 0, (size_t)n * AZ_CHESS_ACTIONS, c->stream));
   }
-  AZC_HIP(hipMemcpyAsync(dpos.p, pos, sizeof(az_chess_pos) * n, hipMemcpyHostToDevice, c->stream));
+  AZ_HIP(hipMemcpyAsync(dpos.p, pos, sizeof(az_chess_pos) * n, hipMemcpyHostToDevice, c->stream));
   legal_kernel<<<n, 64, 0, c->stream>>>(dpos.p, n, dmv.p, dcnt.p, mask ? dmask.p : nullptr,
                                                       outcome_out ? dout.p : nullptr, c->lut);
-  AZC_HIP(hipGetLastError());
-  AZC_HIP(hipMemcpyAsync(counts, dcnt.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
+  AZ_HIP(hipGetLastError());
+  AZ_HIP(hipMemcpyAsync(counts, dcnt.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
   if (moves)
-    AZC_HIP(hipMemcpyAsync(moves, dmv.p, sizeof(uint16_t) * AZ_CHESS_MAX_MOVES * n, hipMemcpyDeviceToHost,
-                           c->stream));
+    AZ_HIP(hipMemcpyAsync(moves, dmv.p, sizeof(uint16_t) * AZ_CHESS_MAX_MOVES * n, hipMemcpyDeviceToHost,
+                          c->stream));
   if (mask)
-    AZC_HIP(hipMemcpyAsync(mask, dmask.p, (size_t)n * AZ_CHESS_ACTIONS, hipMemcpyDeviceToHost, c->stream));
+    AZ_HIP(hipMemcpyAsync(mask, dmask.p, (size_t)n * AZ_CHESS_ACTIONS, hipMemcpyDeviceToHost, c->stream));
   if (outcome_out)
-    AZC_HIP(hipMemcpyAsync(outcome_out, dout.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
-  AZC_HIP(hipStreamSynchronize(c->stream));
+    AZ_HIP(hipMemcpyAsync(outcome_out, dout.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
+  AZ_HIP(hipStreamSynchronize(c->stream));
   for (int i = 0; i < n; ++i)
     if (counts[i] < 0) return az::fail_abi(AZ_E_DEVICE, "az_chess_legal: pseudo-legal move list overflow");
   return AZ_OK;
@@ -320,16 +306,16 @@ extern "C" int az_chess_encode(int device, const az_chess_pos* hist, const uint8
   DBuf<uint8_t> dv;
   DBuf<float> ds;
   size_t per = (size_t)64 * AZ_CHESS_PLANES;
-  AZC_HIP(dh.alloc((size_t)n * AZ_CHESS_HISTORY));
-  AZC_HIP(dv.alloc((size_t)n * AZ_CHESS_HISTORY));
-  AZC_HIP(ds.alloc((size_t)n * per));
-  AZC_HIP(hipMemcpyAsync(dh.p, hist, sizeof(az_chess_pos) * AZ_CHESS_HISTORY * n, hipMemcpyHostToDevice,
-                         c->stream));
-  AZC_HIP(hipMemcpyAsync(dv.p, valid, (size_t)AZ_CHESS_HISTORY * n, hipMemcpyHostToDevice, c->stream));
+  AZ_HIP(dh.alloc((size_t)n * AZ_CHESS_HISTORY));
+  AZ_HIP(dv.alloc((size_t)n * AZ_CHESS_HISTORY));
+  AZ_HIP(ds.alloc((size_t)n * per));
+  AZ_HIP(hipMemcpyAsync(dh.p, hist, sizeof(az_chess_pos) * AZ_CHESS_HISTORY * n, hipMemcpyHostToDevice,
+                        c->stream));
+  AZ_HIP(hipMemcpyAsync(dv.p, valid, (size_t)AZ_CHESS_HISTORY * n, hipMemcpyHostToDevice, c->stream));
   encode_kernel<<<std::min(n, 4096), 256, 0, c->stream>>>(dh.p, dv.p, n, ds.p);
-  AZC_HIP(hipGetLastError());
-  AZC_HIP(hipMemcpyAsync(state, ds.p, sizeof(float) * per * n, hipMemcpyDeviceToHost, c->stream));
-  AZC_HIP(hipStreamSynchronize(c->stream));
+  AZ_HIP(hipGetLastError());
+  AZ_HIP(hipMemcpyAsync(state, ds.p, sizeof(float) * per * n, hipMemcpyDeviceToHost, c->stream));
+  AZ_HIP(hipStreamSynchronize(c->stream));
   return AZ_OK;
 }
 
@@ -340,14 +326,14 @@ extern "C" int az_chess_play(int device, az_chess_pos* pos, const uint16_t* move
   if (int rc = ctx_for(device, &c)) return rc;
   DBuf<az_chess_pos> dp;
   DBuf<uint16_t> dm;
-  AZC_HIP(dp.alloc(n));
-  AZC_HIP(dm.alloc(n));
-  AZC_HIP(hipMemcpyAsync(dp.p, pos, sizeof(az_chess_pos) * n, hipMemcpyHostToDevice, c->stream));
-  AZC_HIP(hipMemcpyAsync(dm.p, moves, sizeof(uint16_t) * n, hipMemcpyHostToDevice, c->stream));
+  AZ_HIP(dp.alloc(n));
+  AZ_HIP(dm.alloc(n));
+  AZ_HIP(hipMemcpyAsync(dp.p, pos, sizeof(az_chess_pos) * n, hipMemcpyHostToDevice, c->stream));
+  AZ_HIP(hipMemcpyAsync(dm.p, moves, sizeof(uint16_t) * n, hipMemcpyHostToDevice, c->stream));
   play_kernel<<<(n + 127) / 128, 128, 0, c->stream>>>(dp.p, dm.p, n, keep_same_player);
-  AZC_HIP(hipGetLastError());
-  AZC_HIP(hipMemcpyAsync(pos, dp.p, sizeof(az_chess_pos) * n, hipMemcpyDeviceToHost, c->stream));
-  AZC_HIP(hipStreamSynchronize(c->stream));
+  AZ_HIP(hipGetLastError());
+  AZ_HIP(hipMemcpyAsync(pos, dp.p, sizeof(az_chess_pos) * n, hipMemcpyDeviceToHost, c->stream));
+  AZ_HIP(hipStreamSynchronize(c->stream));
   return AZ_OK;
 }
 
@@ -360,29 +346,29 @@ extern "C" int az_chess_perft(int device, const az_chess_pos* pos, int depth, ui
   DevCtx* c;
   if (int rc = ctx_for(device, &c)) return rc;
   DBuf<az_chess_pos> level;
-  AZC_HIP(level.alloc(1));
-  AZC_HIP(hipMemcpyAsync(level.p, pos, sizeof(az_chess_pos), hipMemcpyHostToDevice, c->stream));
+  AZ_HIP(level.alloc(1));
+  AZ_HIP(hipMemcpyAsync(level.p, pos, sizeof(az_chess_pos), hipMemcpyHostToDevice, c->stream));
   long long n = 1;
   DBuf<unsigned long long> dtot;
   DBuf<int> derr;
-  AZC_HIP(dtot.alloc(1));
-  AZC_HIP(derr.alloc(1));
-  AZC_HIP(hipMemsetAsync(derr.p, 0, sizeof(int), c->stream));
+  AZ_HIP(dtot.alloc(1));
+  AZ_HIP(derr.alloc(1));
+  AZ_HIP(hipMemsetAsync(derr.p, 0, sizeof(int), c->stream));
   const long long kMaxLevel = 1ll << 26;  // 5.4 GB of positions (+ 34 GB of move lists)
   for (int d = 1; d <= depth; ++d) {
     DBuf<int32_t> cnt;
     DBuf<uint16_t> mv;
-    AZC_HIP(cnt.alloc(n));
-    AZC_HIP(mv.alloc((size_t)n * AZ_CHESS_MAX_MOVES));
-    AZC_HIP(hipMemsetAsync(dtot.p, 0, sizeof(unsigned long long), c->stream));
+    AZ_HIP(cnt.alloc(n));
+    AZ_HIP(mv.alloc((size_t)n * AZ_CHESS_MAX_MOVES));
+    AZ_HIP(hipMemsetAsync(dtot.p, 0, sizeof(unsigned long long), c->stream));
     int blocks = (int)((n + 127) / 128);
     perft_count_kernel<<<blocks, 128, 0, c->stream>>>(level.p, (int)n, mv.p, cnt.p, dtot.p, derr.p);
-    AZC_HIP(hipGetLastError());
+    AZ_HIP(hipGetLastError());
     unsigned long long tot = 0;
     int err = 0;
-    AZC_HIP(hipMemcpyAsync(&tot, dtot.p, sizeof(tot), hipMemcpyDeviceToHost, c->stream));
-    AZC_HIP(hipMemcpyAsync(&err, derr.p, sizeof(err), hipMemcpyDeviceToHost, c->stream));
-    AZC_HIP(hipStreamSynchronize(c->stream));
+    AZ_HIP(hipMemcpyAsync(&tot, dtot.p, sizeof(tot), hipMemcpyDeviceToHost, c->stream));
+    AZ_HIP(hipMemcpyAsync(&err, derr.p, sizeof(err), hipMemcpyDeviceToHost, c->stream));
+    AZ_HIP(hipStreamSynchronize(c->stream));
     if (err) return az::fail_abi(AZ_E_DEVICE, "az_chess_perft: pseudo-legal move list overflow");
     if (d == depth) {
       *nodes = tot;
@@ -392,7 +378,7 @@ extern "C" int az_chess_perft(int device, const az_chess_pos* pos, int depth, ui
     // exclusive scan of the counts on the host (a test utility, not a hot path)
     std::vector<int32_t> hc(n);
     std::vector<long long> ho(n);
-    AZC_HIP(hipMemcpy(hc.data(), cnt.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+    AZ_HIP(hipMemcpy(hc.data(), cnt.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
     long long run = 0;
     for (long long i = 0; i < n; ++i) {
       ho[i] = run;
@@ -400,12 +386,12 @@ extern "C" int az_chess_perft(int device, const az_chess_pos* pos, int depth, ui
     }
     DBuf<long long> doff;
     DBuf<az_chess_pos> next;
-    AZC_HIP(doff.alloc(n));
-    AZC_HIP(next.alloc(run));
-    AZC_HIP(hipMemcpy(doff.p, ho.data(), sizeof(long long) * n, hipMemcpyHostToDevice));
+    AZ_HIP(doff.alloc(n));
+    AZ_HIP(next.alloc(run));
+    AZ_HIP(hipMemcpy(doff.p, ho.data(), sizeof(long long) * n, hipMemcpyHostToDevice));
     perft_expand_kernel<<<blocks, 128, 0, c->stream>>>(level.p, (int)n, mv.p, cnt.p, doff.p, next.p);
-    AZC_HIP(hipGetLastError());
-    AZC_HIP(hipStreamSynchronize(c->stream));
+    AZ_HIP(hipGetLastError());
+    AZ_HIP(hipStreamSynchronize(c->stream));
     std::swap(level.p, next.p);
     n = run;
   }

@@ -30,12 +30,9 @@
 
 #include "../../include/az_chess.h"
 #include "az_chess.h"
+#include "az_host.h"
 #include "az_nn.h"
 #include "az_tree.h"
-
-namespace az {
-int fail_abi(int code, const std::string& msg);
-}
 
 namespace azc {
 std::vector<int16_t> action_lut();  // az_chess.hip
@@ -1033,13 +1030,6 @@ __global__ __launch_bounds__(64) void play_kernel(CCfg g, CTree t, CSamples smp,
   }
 }
 
-#define AZC_HIP(expr)                                                                      \
-  do {                                                                                     \
-    hipError_t err__ = (expr);                                                             \
-    if (err__ != hipSuccess)                                                               \
-      return az::fail_abi(AZ_E_HIP, std::string(#expr) + ": " + hipGetErrorString(err__)); \
-  } while (0)
-
 }  // namespace
 }  // namespace azc
 
@@ -1061,7 +1051,6 @@ struct CLane {
   int32_t* counts = nullptr;  // [2] the eval queue counters, alternating by simulation
   int par = 0;
   bool pending_expand = false;  // the last simulation's expand not launched yet
-  hipEvent_t move_done[4] = {nullptr, nullptr, nullptr, nullptr};  // move m's end on this lane (m % 4)
   ChessCache cache{};  // the engine's (flush_expand has no engine pointer)
 };
 
@@ -1081,16 +1070,12 @@ struct az_chess_engine {
   float* act[3] = {nullptr, nullptr, nullptr};
   float* probs = nullptr;
   float* values = nullptr;
-  std::vector<void*> owned, sample_bufs;
+  az::DeviceAllocs mem;
+  az::DeviceAllocs samples;  // the self-play sample buffers, re-made at every az_chess_selfplay_begin
   int64_t sp_n = 0;
-  // asynchronous steps + drain (ABI 10), as the Connect-N engine: per move m
-  // the last lane to finish it stores the games-finished count into pinned
-  // snap_host[m % 4] (az::launch_move_end); the drain copies the games of the
-  // newest move whose snapshot is complete on pack_stream
-  int64_t moves_issued = 0, batch_first_move = 0, drained = 0;
-  int32_t* move_arrive = nullptr;           // device [4]
-  unsigned long long* snap_dev = nullptr;   // pinned [4] (device view)
-  unsigned long long* snap_host = nullptr;  // its host view
+  // asynchronous steps + drain (ABI 10), as the Connect-N engine: the drain
+  // copies the games of the clock's newest complete snapshot on pack_stream
+  az::MoveClock clock;
   hipStream_t pack_stream = nullptr;
   // tree API staging (allocated on first use)
   double* tree_u = nullptr;
@@ -1098,36 +1083,12 @@ struct az_chess_engine {
   int16_t* tree_pol_a = nullptr;
   double* tree_pol_p = nullptr;
   az_chess_pos* tree_roots = nullptr;
-
-  template <typename T>
-  int alloc(T** p, size_t count) {
-    void* q = nullptr;
-    AZC_HIP(hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T)));
-    owned.push_back(q);
-    *p = reinterpret_cast<T*>(q);
-    return 0;
-  }
 };
 
 namespace {
 
 int check_errors(az_chess_engine* e) {
-  unsigned long long err = 0;
-  AZC_HIP(hipMemcpy(&err, e->t.stats + az::kStatErrors, sizeof(err), hipMemcpyDeviceToHost));
-  if (!err) return 0;
-  std::string m = "device error flags:";
-  if (err & az::kErrArena) m += " arena-overflow(raise az_chess_config.arena_edges)";
-  if (err & az::kErrPow) m += " visit-table-overflow";
-  if (err & az::kErrPath) m += " path-overflow";
-  if (err & az::kErrIllegal) m += " illegal-move";
-  if (err & az::kErrNoRoot) m += " play-before-search";
-  if (err & az::kErrActRange)
-    m += " activation-range(a non-finite activation, or |x| > 32752 in the per-layer fp16x2 convs: "
-         "use conv_algo=AZ_CONV_F16X2 or AZ_CONV_DIRECT)";
-  // play on a slot without a searched root changes nothing: that flag is
-  // cleared once reported (the others mean a broken tree and stay)
-  if (err == az::kErrNoRoot) AZC_HIP(hipMemset(e->t.stats + az::kStatErrors, 0, sizeof(err)));
-  return az::fail_abi(AZ_E_DEVICE, m);
+  return az::device_error_status(e->t.stats, {"(raise az_chess_config.arena_edges)", ""});
 }
 
 int simulate(az_chess_engine* e, CLane& L) {
@@ -1169,7 +1130,7 @@ int simulate(az_chess_engine* e, CLane& L) {
     synth_kernel<<<(S + 255) / 256, 256, 0, s>>>(L.g, L.t, L.probs, L.values);
   }
   L.pending_expand = true;  // in the next simulation's select launch, or flush_expand
-  AZC_HIP(hipGetLastError());
+  AZ_HIP(hipGetLastError());
   return 0;
 }
 
@@ -1178,13 +1139,13 @@ int flush_expand(CLane& L) {
   if (!L.pending_expand) return 0;
   L.pending_expand = false;
   expand_kernel<<<L.g.slots, 64, 0, L.stream>>>(L.g, L.t, L.cache, L.probs, L.values);
-  AZC_HIP(hipGetLastError());
+  AZ_HIP(hipGetLastError());
   return 0;
 }
 
 int sync_lanes(az_chess_engine* e) {
-  for (CLane* L : e->lanes) AZC_HIP(hipStreamSynchronize(L->stream));
-  AZC_HIP(hipStreamSynchronize(e->stream));
+  for (CLane* L : e->lanes) AZ_HIP(hipStreamSynchronize(L->stream));
+  AZ_HIP(hipStreamSynchronize(e->stream));
   return 0;
 }
 
@@ -1217,8 +1178,8 @@ int make_lane(az_chess_engine* e, CLane* L, int first, int n) {
   t.slot_q += f;
   if (t.leaf_pay) t.leaf_pay += f * kPayFloats;
   int rc;
-  if ((rc = e->alloc(&t.eval_count, 4))) return rc;
-  AZC_HIP(hipMemset(t.eval_count, 0, 4 * sizeof(int32_t)));
+  if ((rc = e->mem.alloc(&t.eval_count, 4, false))) return rc;
+  AZ_HIP(hipMemset(t.eval_count, 0, 4 * sizeof(int32_t)));
   L->counts = t.eval_count;
   t.dup_count = t.eval_count + 1;
   t.next_count = t.eval_count + 2;
@@ -1226,11 +1187,11 @@ int make_lane(az_chess_engine* e, CLane* L, int first, int n) {
   // the lane's per-simulation dedup table (load factor <= 25%) and duplicates list
   size_t cap = 256;
   while (cap < 4 * (size_t)n) cap <<= 1;
-  if ((rc = e->alloc(&t.step_tag, cap)) || (rc = e->alloc(&t.step_row, cap)) || (rc = e->alloc(&t.dup_q, n)) ||
-      (rc = e->alloc(&t.sel_done, 1)))
+  if ((rc = e->mem.alloc(&t.step_tag, cap, false)) || (rc = e->mem.alloc(&t.step_row, cap, false)) || (rc = e->mem.alloc(&t.dup_q, n, false)) ||
+      (rc = e->mem.alloc(&t.sel_done, 1, false)))
     return rc;
-  AZC_HIP(hipMemset(t.step_tag, 0, cap * sizeof(uint64_t)));
-  AZC_HIP(hipMemset(t.sel_done, 0, sizeof(uint32_t)));
+  AZ_HIP(hipMemset(t.step_tag, 0, cap * sizeof(uint64_t)));
+  AZ_HIP(hipMemset(t.sel_done, 0, sizeof(uint32_t)));
   t.step_mask = (uint32_t)(cap - 1);
   t.epoch = 0;
   L->cache = e->cache;
@@ -1262,12 +1223,8 @@ int az_chess_engine_create(int device, const az_chess_config* cfg, az_chess_engi
     return az::fail_abi(AZ_E_INVALID, "negative bound");
   if ((int64_t)c.slots * 64 * 512 >= (1ll << 31))
     return az::fail_abi(AZ_E_INVALID, "slots * 64 * 512 must stay below 2^31 (32-bit activation byte offsets)");
-  int dev_count = 0;
-  if (hipGetDeviceCount(&dev_count) != hipSuccess || dev_count == 0)
-    return az::fail_abi(AZ_E_HIP, "no HIP device visible: libaz has no CPU fallback");
-  if (device < 0 || device >= dev_count) return az::fail_abi(AZ_E_INVALID, "bad device index");
-  AZC_HIP(hipSetDevice(device));
-  AZC_HIP(upload_rays());
+  AZ_TRY(az::open_device(device));
+  AZ_HIP(upload_rays());
   az_chess_engine* e = new az_chess_engine();
   e->device = device;
   e->cfg = c;
@@ -1296,30 +1253,28 @@ int az_chess_engine_create(int device, const az_chess_config* cfg, az_chess_engi
   const size_t S = (size_t)g.slots;
   CTree& t = e->t;
   int rc;
-  if ((rc = e->alloc(&t.edges, S * 2 * (size_t)g.half_cap)) || (rc = e->alloc(&t.root, S)) ||
-      (rc = e->alloc(&t.root_first, S)) || (rc = e->alloc(&t.root_n, S)) || (rc = e->alloc(&t.half, S)) ||
-      (rc = e->alloc(&t.top, S)) || (rc = e->alloc(&t.ply, S)) || (rc = e->alloc(&t.initial, S)) ||
-      (rc = e->alloc(&t.game_id, S)) || (rc = e->alloc(&t.path, S * g.max_depth)) ||
-      (rc = e->alloc(&t.path_len, S)) || (rc = e->alloc(&t.leaf, S)) ||
-      (rc = e->alloc(&t.leaf_moves, S * AZ_CHESS_MAX_MOVES)) || (rc = e->alloc(&t.leaf_n, S)) ||
-      (rc = e->alloc(&t.slot_exp, S)) || (rc = e->alloc(&t.root_value, S)) ||
-      (rc = e->alloc(&t.mt, S * (kMtN + 1))) ||
-      (rc = e->alloc(&t.eval_slot, S)) || (rc = e->alloc(&t.eval_count, 1)) || (rc = e->alloc(&t.slot_q, S)) ||
-      (rc = e->alloc(&t.stats, az::kStatCount)))
+  if ((rc = e->mem.alloc(&t.edges, S * 2 * (size_t)g.half_cap, false)) || (rc = e->mem.alloc(&t.root, S, false)) ||
+      (rc = e->mem.alloc(&t.root_first, S, false)) || (rc = e->mem.alloc(&t.root_n, S, false)) || (rc = e->mem.alloc(&t.half, S, false)) ||
+      (rc = e->mem.alloc(&t.top, S, false)) || (rc = e->mem.alloc(&t.ply, S, false)) || (rc = e->mem.alloc(&t.initial, S, false)) ||
+      (rc = e->mem.alloc(&t.game_id, S, false)) || (rc = e->mem.alloc(&t.path, S * g.max_depth, false)) ||
+      (rc = e->mem.alloc(&t.path_len, S, false)) || (rc = e->mem.alloc(&t.leaf, S, false)) ||
+      (rc = e->mem.alloc(&t.leaf_moves, S * AZ_CHESS_MAX_MOVES, false)) || (rc = e->mem.alloc(&t.leaf_n, S, false)) ||
+      (rc = e->mem.alloc(&t.slot_exp, S, false)) || (rc = e->mem.alloc(&t.root_value, S, false)) ||
+      (rc = e->mem.alloc(&t.mt, S * (kMtN + 1), false)) ||
+      (rc = e->mem.alloc(&t.eval_slot, S, false)) || (rc = e->mem.alloc(&t.eval_count, 1, false)) || (rc = e->mem.alloc(&t.slot_q, S, false)) ||
+      (rc = e->mem.alloc(&t.stats, az::kStatCount, false)))
     return cleanup(rc);
   t.next_count = t.eval_count;  // (the lanes' views carry their own pair)
   {
     double* powtab = nullptr;
-    if ((rc = e->alloc(&powtab, g.pow_len))) return cleanup(rc);
-    std::vector<double> hp(g.pow_len);
-    double (*volatile pw)(double, double) = pow;  // libm pow, as Python `** 0.5` (mcts.py:50)
-    for (int k = 0; k < g.pow_len; ++k) hp[k] = k == 0 ? 0.0 : pw((double)k, 0.5);
+    if ((rc = e->mem.alloc(&powtab, g.pow_len, false))) return cleanup(rc);
+    const std::vector<double> hp = az::sqrt_pow_table(g.pow_len);
     if (hipMemcpy(powtab, hp.data(), hp.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
       return cleanup(az::fail_abi(AZ_E_HIP, "pow table upload failed"));
     t.powtab = powtab;
     int16_t* lut = nullptr;
     std::vector<int16_t> hl = action_lut();
-    if ((rc = e->alloc(&lut, hl.size()))) return cleanup(rc);
+    if ((rc = e->mem.alloc(&lut, hl.size(), false))) return cleanup(rc);
     if (hipMemcpy(lut, hl.data(), hl.size() * sizeof(int16_t), hipMemcpyHostToDevice) != hipSuccess)
       return cleanup(az::fail_abi(AZ_E_HIP, "action table upload failed"));
     t.lut = lut;
@@ -1327,13 +1282,13 @@ int az_chess_engine_create(int device, const az_chess_config* cfg, az_chess_engi
   if (hipMemset(t.stats, 0, az::kStatCount * sizeof(unsigned long long)) != hipSuccess ||
       hipMemset(t.game_id, 0xff, S * sizeof(int64_t)) != hipSuccess)
     return cleanup(az::fail_abi(AZ_E_HIP, "memset failed"));
-  if ((rc = e->alloc(&e->probs, S * AZ_CHESS_ACTIONS)) || (rc = e->alloc(&e->values, S))) return cleanup(rc);
+  if ((rc = e->mem.alloc(&e->probs, S * AZ_CHESS_ACTIONS, false)) || (rc = e->mem.alloc(&e->values, S, false))) return cleanup(rc);
   if (c.evaluator == AZ_EVAL_NETWORK) {
-    if ((rc = e->alloc(&e->x, S * 64 * 128))) return cleanup(rc);
+    if ((rc = e->mem.alloc(&e->x, S * 64 * 128, false))) return cleanup(rc);
     if (hipMemset(e->x, 0, S * 64 * 128 * sizeof(float)) != hipSuccess)
       return cleanup(az::fail_abi(AZ_E_HIP, "memset failed"));
     for (int i = 0; i < 3; ++i)
-      if ((rc = e->alloc(&e->act[i], S * 64 * 128))) return cleanup(rc);
+      if ((rc = e->mem.alloc(&e->act[i], S * 64 * 128, false))) return cleanup(rc);
   }
   t.mt_stride = g.slots;
   // the transposition cache (mcts.py:122-143 on chess boards)
@@ -1343,9 +1298,9 @@ int az_chess_engine_create(int device, const az_chess_config* cfg, az_chess_engi
   if (c.cache_log2 > 0) {
     const size_t cap = (size_t)1 << c.cache_log2;
     ChessCache& cc = e->cache;
-    if ((rc = e->alloc(&cc.keys, cap)) || (rc = e->alloc(&cc.state, cap)) ||
-        (rc = e->alloc(&cc.pay, cap * kPayFloats)) || (rc = e->alloc(&cc.ctl, 4)) ||
-        (rc = e->alloc(&t.leaf_pay, S * kPayFloats)))
+    if ((rc = e->mem.alloc(&cc.keys, cap, false)) || (rc = e->mem.alloc(&cc.state, cap, false)) ||
+        (rc = e->mem.alloc(&cc.pay, cap * kPayFloats, false)) || (rc = e->mem.alloc(&cc.ctl, 4, false)) ||
+        (rc = e->mem.alloc(&t.leaf_pay, S * kPayFloats, false)))
       return cleanup(rc);
     cc.mask = (uint32_t)(cap - 1);
     cc.enabled = 1;
@@ -1380,18 +1335,11 @@ int az_chess_engine_create(int device, const az_chess_config* cfg, az_chess_engi
     e->lanes.push_back(L);
     const int lo = (int)((int64_t)g.slots * l / nl), hi = (int)((int64_t)g.slots * (l + 1) / nl);
     if ((rc = make_lane(e, L, lo, hi - lo))) return cleanup(rc);
-    for (hipEvent_t& ev : L->move_done)
-      if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess)
-        return cleanup(az::fail_abi(AZ_E_HIP, "hipEventCreate failed"));
   }
   // the drain's move snapshots (pinned, coherent) and its own stream
-  if ((rc = e->alloc(&e->move_arrive, 4))) return cleanup(rc);
-  if (hipMemset(e->move_arrive, 0, 4 * sizeof(int32_t)) != hipSuccess ||
-      hipHostMalloc(&e->snap_host, 4 * sizeof(unsigned long long), hipHostMallocCoherent) != hipSuccess ||
-      hipHostGetDevicePointer((void**)&e->snap_dev, e->snap_host, 0) != hipSuccess ||
-      hipStreamCreateWithFlags(&e->pack_stream, hipStreamNonBlocking) != hipSuccess)
+  if ((rc = e->clock.create(e->mem, nl, "drain snapshot allocation failed"))) return cleanup(rc);
+  if (hipStreamCreateWithFlags(&e->pack_stream, hipStreamNonBlocking) != hipSuccess)
     return cleanup(az::fail_abi(AZ_E_HIP, "drain snapshot allocation failed"));
-  for (int i = 0; i < 4; ++i) e->snap_host[i] = 0;
   *out = e;
   return 0;
 }
@@ -1405,17 +1353,15 @@ int az_chess_engine_destroy(az_chess_engine* e) {
       (void)hipStreamSynchronize(L->stream);
       (void)hipStreamDestroy(L->stream);
     }
-    for (hipEvent_t ev : L->move_done)
-      if (ev) (void)hipEventDestroy(ev);
     delete L;
   }
   if (e->pack_stream) {
     (void)hipStreamSynchronize(e->pack_stream);
     (void)hipStreamDestroy(e->pack_stream);
   }
-  if (e->snap_host) (void)hipHostFree(e->snap_host);
-  for (void* p : e->sample_bufs) (void)hipFree(p);
-  for (void* p : e->owned) (void)hipFree(p);
+  e->clock.destroy();
+  e->samples.free_all();
+  e->mem.free_all();
   if (e->timer_ref) (void)hipEventDestroy(e->timer_ref);
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
@@ -1425,37 +1371,37 @@ int az_chess_engine_destroy(az_chess_engine* e) {
 int az_chess_engine_set_weights(az_chess_engine* e, const az_tensor* tensors, int n) {
   if (!e || (!tensors && n)) return az::fail_abi(AZ_E_INVALID, "null argument");
   if (e->cfg.evaluator != AZ_EVAL_NETWORK) return az::fail_abi(AZ_E_STATE, "engine has no network evaluator");
-  AZC_HIP(hipSetDevice(e->device));
+  AZ_HIP(hipSetDevice(e->device));
   int rc;
   if ((rc = sync_lanes(e))) return rc;
   if (e->cache.state) {  // a new model empties plays_inferences (self_play.py:145-146)
-    AZC_HIP(hipMemset(e->cache.state, 0, ((size_t)e->cache.mask + 1) * sizeof(uint32_t)));
-    AZC_HIP(hipMemset(e->cache.ctl, 0, 4 * sizeof(unsigned long long)));
+    AZ_HIP(hipMemset(e->cache.state, 0, ((size_t)e->cache.mask + 1) * sizeof(uint32_t)));
+    AZ_HIP(hipMemset(e->cache.ctl, 0, 4 * sizeof(unsigned long long)));
   }
   return az::load_network(e->net, tensors, n, AZ_CHESS_PLANES, 64, AZ_CHESS_ACTIONS, e->cfg.bn_epsilon,
-                          e->owned);
+                          e->mem);
 }
 
 int az_chess_forward(az_chess_engine* e, const float* x, int n, float* probs, float* values) {
   if (!e || n < 0 || (n && (!x || !probs || !values))) return az::fail_abi(AZ_E_INVALID, "bad arguments");
   if (!e->net.ready) return az::fail_abi(AZ_E_STATE, "az_chess_engine_set_weights was not called");
-  AZC_HIP(hipSetDevice(e->device));
+  AZ_HIP(hipSetDevice(e->device));
   const int chunk = e->g.slots;
   for (int off = 0; off < n; off += chunk) {
     const int m = std::min(chunk, n - off);
     // [m][64][118] -> the network input [m][64][128] (planes 118..127 zero), split16 for the
     // fp16x2 convs; act[2] stages the host floats (the forward writes it only after the stem)
     float* staging = static_cast<float*>(e->act[2]);
-    AZC_HIP(hipMemcpyAsync(staging, x + (size_t)off * 64 * AZ_CHESS_PLANES,
-                           (size_t)m * 64 * AZ_CHESS_PLANES * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    AZ_HIP(hipMemcpyAsync(staging, x + (size_t)off * 64 * AZ_CHESS_PLANES,
+                          (size_t)m * 64 * AZ_CHESS_PLANES * sizeof(float), hipMemcpyHostToDevice, e->stream));
     az::launch_pad_rows(staging, m * 64, AZ_CHESS_PLANES, e->x, e->net.algo == AZ_CONV_F16X2, e->stream);
     az::launch_forward(e->net, e->x, nullptr, m, 8, 8, AZ_CHESS_ACTIONS, e->act[0], e->act[1], e->act[2],
                        e->probs, e->values, e->stream, e->timer.enabled ? &e->timer : nullptr);
-    AZC_HIP(hipGetLastError());
-    AZC_HIP(hipMemcpyAsync(probs + (size_t)off * AZ_CHESS_ACTIONS, e->probs,
-                           (size_t)m * AZ_CHESS_ACTIONS * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-    AZC_HIP(hipMemcpyAsync(values + off, e->values, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-    AZC_HIP(hipStreamSynchronize(e->stream));
+    AZ_HIP(hipGetLastError());
+    AZ_HIP(hipMemcpyAsync(probs + (size_t)off * AZ_CHESS_ACTIONS, e->probs,
+                          (size_t)m * AZ_CHESS_ACTIONS * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    AZ_HIP(hipMemcpyAsync(values + off, e->values, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    AZ_HIP(hipStreamSynchronize(e->stream));
   }
   return 0;
 }
@@ -1464,12 +1410,11 @@ int az_chess_selfplay_begin(az_chess_engine* e, int64_t first_game, int64_t n_ga
   if (!e || n_games < 0 || first_game < 0) return az::fail_abi(AZ_E_INVALID, "bad arguments");
   if (e->cfg.evaluator == AZ_EVAL_NETWORK && !e->net.ready)
     return az::fail_abi(AZ_E_STATE, "network evaluator selected but az_chess_engine_set_weights was not called");
-  AZC_HIP(hipSetDevice(e->device));
+  AZ_HIP(hipSetDevice(e->device));
   for (CLane* L : e->lanes) L->pending_expand = false;  // (a search an error interrupted)
   int rc;
   if ((rc = sync_lanes(e))) return rc;
-  for (void* p : e->sample_bufs) (void)hipFree(p);
-  e->sample_bufs.clear();
+  e->samples.free_all();
   CSamples& smp = e->smp;
   smp = CSamples{};
   smp.first_game = first_game;
@@ -1477,118 +1422,64 @@ int az_chess_selfplay_begin(az_chess_engine* e, int64_t first_game, int64_t n_ga
   smp.base_seed = base_seed;
   smp.plies = e->g.max_plies;
   const size_t G = (size_t)std::max<int64_t>(n_games, 1), P = (size_t)smp.plies, M = AZ_CHESS_MAX_MOVES;
-  auto get = [&](void** p, size_t bytes) -> int {
-    AZC_HIP(hipMalloc(p, std::max<size_t>(bytes, 16)));
-    e->sample_bufs.push_back(*p);
-    AZC_HIP(hipMemsetAsync(*p, 0, std::max<size_t>(bytes, 16), e->stream));
-    return 0;
-  };
-  if ((rc = get((void**)&smp.pos, G * P * sizeof(az_chess_pos))) ||
-      (rc = get((void**)&smp.moves, G * P * sizeof(uint16_t))) ||
-      (rc = get((void**)&smp.pol_n, G * P * sizeof(int32_t))) ||
-      (rc = get((void**)&smp.pol_a, G * P * M * sizeof(int16_t))) ||
-      (rc = get((void**)&smp.pol_p, G * P * M * sizeof(double))) ||
-      (rc = get((void**)&smp.length, G * sizeof(int32_t))) || (rc = get((void**)&smp.result, G * sizeof(int32_t))) ||
-      (rc = get((void**)&smp.term, G * sizeof(int32_t))) || (rc = get((void**)&smp.expansions, G * sizeof(int32_t))) ||
-      (rc = get((void**)&smp.done_ids, G * sizeof(int64_t))) ||
-      (rc = get((void**)&smp.done_count, sizeof(unsigned long long))))
+  az::DeviceAllocs& sb = e->samples;
+  hipStream_t s = e->stream;
+  if ((rc = sb.alloc_zeroed_async(&smp.pos, G * P, s)) || (rc = sb.alloc_zeroed_async(&smp.moves, G * P, s)) ||
+      (rc = sb.alloc_zeroed_async(&smp.pol_n, G * P, s)) || (rc = sb.alloc_zeroed_async(&smp.pol_a, G * P * M, s)) ||
+      (rc = sb.alloc_zeroed_async(&smp.pol_p, G * P * M, s)) || (rc = sb.alloc_zeroed_async(&smp.length, G, s)) ||
+      (rc = sb.alloc_zeroed_async(&smp.result, G, s)) || (rc = sb.alloc_zeroed_async(&smp.term, G, s)) ||
+      (rc = sb.alloc_zeroed_async(&smp.expansions, G, s)) || (rc = sb.alloc_zeroed_async(&smp.done_ids, G, s)) ||
+      (rc = sb.alloc_zeroed_async(&smp.done_count, 1, s)))
     return rc;
-  e->drained = 0;
-  e->batch_first_move = e->moves_issued;
+  e->clock.begin_batch();
   unsigned long long st[az::kStatCount] = {0};
   const int64_t first_wave = std::min<int64_t>(n_games, e->g.slots);
   st[az::kStatNextGame] = (unsigned long long)(first_game + first_wave);
-  AZC_HIP(hipMemcpyAsync(e->t.stats, st, sizeof(st), hipMemcpyHostToDevice, e->stream));
+  AZ_HIP(hipMemcpyAsync(e->t.stats, st, sizeof(st), hipMemcpyHostToDevice, e->stream));
   slot_init_kernel<<<(e->g.slots + 255) / 256, 256, 0, e->stream>>>(e->g, e->t, smp, first_wave);
-  AZC_HIP(hipGetLastError());
-  AZC_HIP(hipStreamSynchronize(e->stream));
+  AZ_HIP(hipGetLastError());
+  AZ_HIP(hipStreamSynchronize(e->stream));
   e->sp_n = n_games;
   return 0;
 }
 
 int az_chess_stats(az_chess_engine* e, az_stats* st) {
   if (!e || !st) return az::fail_abi(AZ_E_INVALID, "null argument");
-  AZC_HIP(hipSetDevice(e->device));
+  AZ_HIP(hipSetDevice(e->device));
   int rc;
   if ((rc = sync_lanes(e))) return rc;
   unsigned long long h[az::kStatCount];
-  AZC_HIP(hipMemcpy(h, e->t.stats, sizeof(h), hipMemcpyDeviceToHost));
-  std::vector<int64_t> gid(e->g.slots);
-  AZC_HIP(hipMemcpy(gid.data(), e->t.game_id, gid.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
-  memset(st, 0, sizeof(*st));
-  st->expansions = (int64_t)h[az::kStatExpansions];
-  st->terminal_visits = (int64_t)h[az::kStatTerminal];
-  st->games_done = (int64_t)h[az::kStatGamesDone];
-  st->simulations = (int64_t)h[az::kStatSims];
-  st->plies = (int64_t)h[az::kStatPlies];
-  st->errors = (int64_t)h[az::kStatErrors];
-  st->evaluations = (int64_t)h[az::kStatNNEvals];
-  st->cache_hits = (int64_t)h[az::kStatCacheHits];
-  if (e->cache.ctl) {
-    unsigned long long ctl[3];
-    AZC_HIP(hipMemcpy(ctl, e->cache.ctl, sizeof(ctl), hipMemcpyDeviceToHost));
-    st->cache_generation = (int64_t)ctl[0];
-    st->cache_inserts = (int64_t)ctl[1];
-    st->cache_entries = (int64_t)ctl[2];
-    st->cache_gen_size = (int64_t)e->cache.gen_size;
-    st->cache_capacity = (int64_t)e->cache.mask + 1;
-  }
+  if ((rc = az::read_common_stats(st, h, e->t.stats, e->t.game_id, e->g.slots, e->cache.ctl, e->cache.gen_size,
+                                  e->cache.mask)))
+    return rc;
   st->issued_flop_per_board = e->net.use_tower && e->net.tower ? e->net.issued_flop_per_board : 0.0;
   st->tower_small_max_boards = -1;  // (chess: one tile height)
-  st->active_slots = std::count_if(gid.begin(), gid.end(), [](int64_t v) { return v >= 0; });
-  // conv-busy time = union of the timed conv intervals over all lanes
   std::vector<az::ConvTimer*> timers = {&e->timer};
   for (CLane* L : e->lanes) timers.push_back(&L->timer);
-  std::vector<std::pair<double, double>> iv;
-  for (az::ConvTimer* tm : timers) {
-    tm->flush();
-    st->conv_ms += tm->total_ms;
-    st->conv_launches += tm->launches;
-    iv.insert(iv.end(), tm->intervals.begin(), tm->intervals.end());
-  }
-  std::sort(iv.begin(), iv.end());
-  double busy = 0.0, lo = 0.0, hi = -1.0;
-  for (const auto& x : iv) {
-    if (x.first > hi) {
-      if (hi > lo) busy += hi - lo;
-      lo = x.first;
-      hi = x.second;
-    } else {
-      hi = std::max(hi, x.second);
-    }
-  }
-  if (hi > lo) busy += hi - lo;
-  st->conv_busy_ms = busy;
+  az::conv_busy_union(timers, st);
   return 0;
 }
 
 int az_chess_selfplay_step(az_chess_engine* e, int n_moves, az_stats* st) {
   if (!e || n_moves < 0) return az::fail_abi(AZ_E_INVALID, "bad arguments");
   if (!e->smp.done_count) return az::fail_abi(AZ_E_STATE, "az_chess_selfplay_begin was not called");
-  AZC_HIP(hipSetDevice(e->device));
+  AZ_HIP(hipSetDevice(e->device));
   int rc;
-  const bool multi = e->lanes.size() > 1;
   for (int mv = 0; mv < n_moves; ++mv) {
-    const int64_t m = e->moves_issued++;
+    const int64_t m = e->clock.issued++;
     // lanes interleaved per simulation so every stream always has work queued
     for (int s = 0; s < e->g.sims; ++s)
       for (CLane* L : e->lanes)
         if ((rc = simulate(e, *L))) return rc;
     for (CLane* L : e->lanes)
       if ((rc = flush_expand(*L))) return rc;
-    for (CLane* L : e->lanes) {
-      // a lane plays move m once every other lane has finished move m - 1, so
-      // move m - 1's games-finished snapshot holds no game of move m (the
-      // drain's contract, as the Connect-N engine's)
-      if (multi && m > e->batch_first_move)
-        for (CLane* O : e->lanes)
-          if (O != L) AZC_HIP(hipStreamWaitEvent(L->stream, O->move_done[(m - 1) % 4], 0));
+    for (size_t l = 0; l < e->lanes.size(); ++l) {
+      CLane* L = e->lanes[l];
+      if ((rc = e->clock.before_play(m, l, L->stream))) return rc;
       play_kernel<<<L->g.slots, 64, 0, L->stream>>>(L->g, L->t, e->smp, CPlayOut{});
-      az::launch_move_end(e->move_arrive + m % 4, (int)e->lanes.size(), e->smp.done_count, e->snap_dev + m % 4,
-                          L->stream);
-      AZC_HIP(hipEventRecord(L->move_done[m % 4], L->stream));
+      if ((rc = e->clock.after_play(m, l, L->stream, e->smp.done_count))) return rc;
     }
-    AZC_HIP(hipGetLastError());
+    AZ_HIP(hipGetLastError());
   }
   if (!st) return 0;  // asynchronous (ABI 10): the moves run on while the caller drains earlier ones
   if ((rc = sync_lanes(e))) return rc;
@@ -1603,30 +1494,16 @@ int az_chess_selfplay_drain(az_chess_engine* e, int64_t max_games, int64_t* n_ou
   if (!e || !n_out || max_games < 0) return az::fail_abi(AZ_E_INVALID, "bad arguments");
   *n_out = 0;
   if (!e->smp.done_count) return 0;  // no self-play batch begun
-  AZC_HIP(hipSetDevice(e->device));
-  // the newest move whose count snapshot is complete; if the last issued move
-  // is still running, wait for the one before it (never for the running one)
-  const int64_t last = e->moves_issued - 1;
-  int64_t k = -1;
-  bool last_done = last >= e->batch_first_move;
-  if (last_done)
-    for (CLane* L : e->lanes) last_done = last_done && hipEventQuery(L->move_done[last % 4]) == hipSuccess;
-  if (last_done) {
-    k = last;
-  } else if (last - 1 >= e->batch_first_move) {
-    k = last - 1;
-    for (CLane* L : e->lanes) AZC_HIP(hipEventSynchronize(L->move_done[k % 4]));
-  }
-  if (k < 0) return 0;
-  const unsigned long long done = __atomic_load_n(e->snap_host + k % 4, __ATOMIC_ACQUIRE);
-  const int64_t n = std::min<int64_t>((int64_t)done - e->drained, max_games);
+  AZ_HIP(hipSetDevice(e->device));
+  int64_t n = 0;
+  if (int rc = e->clock.drainable(max_games, &n)) return rc;
   if (n <= 0) return 0;
   // the finished games' ids, then each game's records (complete once its id
   // is listed: the play kernel stores them first); pack_stream holds nothing else
   std::vector<int64_t> ids((size_t)n);
-  AZC_HIP(hipMemcpyAsync(ids.data(), e->smp.done_ids + e->drained, (size_t)n * sizeof(int64_t),
-                         hipMemcpyDeviceToHost, e->pack_stream));
-  AZC_HIP(hipStreamSynchronize(e->pack_stream));
+  AZ_HIP(hipMemcpyAsync(ids.data(), e->smp.done_ids + e->clock.drained, (size_t)n * sizeof(int64_t),
+                        hipMemcpyDeviceToHost, e->pack_stream));
+  AZ_HIP(hipStreamSynchronize(e->pack_stream));
   const CSamples& s = e->smp;
   const size_t P = (size_t)s.plies, M = AZ_CHESS_MAX_MOVES;
   hipStream_t q = e->pack_stream;
@@ -1634,26 +1511,26 @@ int az_chess_selfplay_drain(az_chess_engine* e, int64_t max_games, int64_t* n_ou
     const int64_t gi = ids[(size_t)i] - s.first_game;
     if (gi < 0 || gi >= s.n_games) return az::fail_abi(AZ_E_STATE, "drained game id outside the batch");
     if (game_ids) game_ids[i] = ids[(size_t)i];
-    if (lengths) AZC_HIP(hipMemcpyAsync(lengths + i, s.length + gi, sizeof(int32_t), hipMemcpyDeviceToHost, q));
-    if (results) AZC_HIP(hipMemcpyAsync(results + i, s.result + gi, sizeof(int32_t), hipMemcpyDeviceToHost, q));
+    if (lengths) AZ_HIP(hipMemcpyAsync(lengths + i, s.length + gi, sizeof(int32_t), hipMemcpyDeviceToHost, q));
+    if (results) AZ_HIP(hipMemcpyAsync(results + i, s.result + gi, sizeof(int32_t), hipMemcpyDeviceToHost, q));
     if (terminations)
-      AZC_HIP(hipMemcpyAsync(terminations + i, s.term + gi, sizeof(int32_t), hipMemcpyDeviceToHost, q));
+      AZ_HIP(hipMemcpyAsync(terminations + i, s.term + gi, sizeof(int32_t), hipMemcpyDeviceToHost, q));
     if (expansions)
-      AZC_HIP(hipMemcpyAsync(expansions + i, s.expansions + gi, sizeof(int32_t), hipMemcpyDeviceToHost, q));
+      AZ_HIP(hipMemcpyAsync(expansions + i, s.expansions + gi, sizeof(int32_t), hipMemcpyDeviceToHost, q));
     if (positions)
-      AZC_HIP(hipMemcpyAsync(positions + i * P, s.pos + gi * P, P * sizeof(az_chess_pos), hipMemcpyDeviceToHost, q));
-    if (moves) AZC_HIP(hipMemcpyAsync(moves + i * P, s.moves + gi * P, P * sizeof(uint16_t), hipMemcpyDeviceToHost, q));
+      AZ_HIP(hipMemcpyAsync(positions + i * P, s.pos + gi * P, P * sizeof(az_chess_pos), hipMemcpyDeviceToHost, q));
+    if (moves) AZ_HIP(hipMemcpyAsync(moves + i * P, s.moves + gi * P, P * sizeof(uint16_t), hipMemcpyDeviceToHost, q));
     if (policy_n)
-      AZC_HIP(hipMemcpyAsync(policy_n + i * P, s.pol_n + gi * P, P * sizeof(int32_t), hipMemcpyDeviceToHost, q));
+      AZ_HIP(hipMemcpyAsync(policy_n + i * P, s.pol_n + gi * P, P * sizeof(int32_t), hipMemcpyDeviceToHost, q));
     if (policy_actions)
-      AZC_HIP(hipMemcpyAsync(policy_actions + i * P * M, s.pol_a + gi * P * M, P * M * sizeof(int16_t),
-                             hipMemcpyDeviceToHost, q));
+      AZ_HIP(hipMemcpyAsync(policy_actions + i * P * M, s.pol_a + gi * P * M, P * M * sizeof(int16_t),
+                            hipMemcpyDeviceToHost, q));
     if (policy_probs)
-      AZC_HIP(hipMemcpyAsync(policy_probs + i * P * M, s.pol_p + gi * P * M, P * M * sizeof(double),
-                             hipMemcpyDeviceToHost, q));
+      AZ_HIP(hipMemcpyAsync(policy_probs + i * P * M, s.pol_p + gi * P * M, P * M * sizeof(double),
+                            hipMemcpyDeviceToHost, q));
   }
-  AZC_HIP(hipStreamSynchronize(q));
-  e->drained += n;
+  AZ_HIP(hipStreamSynchronize(q));
+  e->clock.drained += n;
   *n_out = n;
   return 0;
 }
@@ -1675,22 +1552,22 @@ int az_chess_selfplay_results(az_chess_engine* e, int32_t* lengths, int32_t* res
                               int32_t* expansions, az_chess_pos* positions, uint16_t* moves, int32_t* policy_n,
                               int16_t* policy_actions, double* policy_probs) {
   if (!e) return az::fail_abi(AZ_E_INVALID, "null engine");
-  AZC_HIP(hipSetDevice(e->device));
+  AZ_HIP(hipSetDevice(e->device));
   int rc;
   if ((rc = sync_lanes(e))) return rc;
   const size_t G = (size_t)e->sp_n, P = (size_t)e->smp.plies, M = AZ_CHESS_MAX_MOVES;
   if (G == 0) return 0;
   const CSamples& s = e->smp;
-  if (lengths) AZC_HIP(hipMemcpy(lengths, s.length, G * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (results) AZC_HIP(hipMemcpy(results, s.result, G * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (terminations) AZC_HIP(hipMemcpy(terminations, s.term, G * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (expansions) AZC_HIP(hipMemcpy(expansions, s.expansions, G * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (positions) AZC_HIP(hipMemcpy(positions, s.pos, G * P * sizeof(az_chess_pos), hipMemcpyDeviceToHost));
-  if (moves) AZC_HIP(hipMemcpy(moves, s.moves, G * P * sizeof(uint16_t), hipMemcpyDeviceToHost));
-  if (policy_n) AZC_HIP(hipMemcpy(policy_n, s.pol_n, G * P * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (lengths) AZ_HIP(hipMemcpy(lengths, s.length, G * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (results) AZ_HIP(hipMemcpy(results, s.result, G * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (terminations) AZ_HIP(hipMemcpy(terminations, s.term, G * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (expansions) AZ_HIP(hipMemcpy(expansions, s.expansions, G * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (positions) AZ_HIP(hipMemcpy(positions, s.pos, G * P * sizeof(az_chess_pos), hipMemcpyDeviceToHost));
+  if (moves) AZ_HIP(hipMemcpy(moves, s.moves, G * P * sizeof(uint16_t), hipMemcpyDeviceToHost));
+  if (policy_n) AZ_HIP(hipMemcpy(policy_n, s.pol_n, G * P * sizeof(int32_t), hipMemcpyDeviceToHost));
   if (policy_actions)
-    AZC_HIP(hipMemcpy(policy_actions, s.pol_a, G * P * M * sizeof(int16_t), hipMemcpyDeviceToHost));
-  if (policy_probs) AZC_HIP(hipMemcpy(policy_probs, s.pol_p, G * P * M * sizeof(double), hipMemcpyDeviceToHost));
+    AZ_HIP(hipMemcpy(policy_actions, s.pol_a, G * P * M * sizeof(int16_t), hipMemcpyDeviceToHost));
+  if (policy_probs) AZ_HIP(hipMemcpy(policy_probs, s.pol_p, G * P * M * sizeof(double), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -1699,10 +1576,10 @@ int tree_buffers(az_chess_engine* e) {
   if (e->tree_move) return 0;
   const size_t S = (size_t)e->g.slots, M = AZ_CHESS_MAX_MOVES;
   int rc;
-  if ((rc = e->alloc(&e->tree_u, S)) || (rc = e->alloc(&e->tree_status, S)) || (rc = e->alloc(&e->tree_pol_n, S)) ||
-      (rc = e->alloc(&e->tree_slots, S)) || (rc = e->alloc(&e->tree_pol_a, S * M)) ||
-      (rc = e->alloc(&e->tree_pol_p, S * M)) || (rc = e->alloc(&e->tree_roots, S)) ||
-      (rc = e->alloc(&e->tree_move, S)))
+  if ((rc = e->mem.alloc(&e->tree_u, S, false)) || (rc = e->mem.alloc(&e->tree_status, S, false)) || (rc = e->mem.alloc(&e->tree_pol_n, S, false)) ||
+      (rc = e->mem.alloc(&e->tree_slots, S, false)) || (rc = e->mem.alloc(&e->tree_pol_a, S * M, false)) ||
+      (rc = e->mem.alloc(&e->tree_pol_p, S * M, false)) || (rc = e->mem.alloc(&e->tree_roots, S, false)) ||
+      (rc = e->mem.alloc(&e->tree_move, S, false)))
     return rc;
   return 0;
 }
@@ -1717,7 +1594,7 @@ int tree_slot_list(az_chess_engine* e, int n, const int32_t* slots) {
   }
   int rc;
   if ((rc = tree_buffers(e))) return rc;
-  if (n) AZC_HIP(hipMemcpyAsync(e->tree_slots, slots, n * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+  if (n) AZ_HIP(hipMemcpyAsync(e->tree_slots, slots, n * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
   return 0;
 }
 }  // namespace
@@ -1726,7 +1603,7 @@ int az_chess_tree_reset(az_chess_engine* e, int n, const int32_t* slots, const a
   if (!e || (n && !roots)) return az::fail_abi(AZ_E_INVALID, "null argument");
   if (e->cfg.evaluator == AZ_EVAL_NETWORK && !e->net.ready)
     return az::fail_abi(AZ_E_STATE, "network evaluator selected but az_chess_engine_set_weights was not called");
-  AZC_HIP(hipSetDevice(e->device));
+  AZ_HIP(hipSetDevice(e->device));
   for (CLane* L : e->lanes) L->pending_expand = false;  // (a search an error interrupted)
   int rc;
   if ((rc = sync_lanes(e)) || (rc = tree_slot_list(e, n, slots))) return rc;
@@ -1736,22 +1613,22 @@ int az_chess_tree_reset(az_chess_engine* e, int n, const int32_t* slots, const a
   for (const az_chess_pos& p : r)
     if (p.turn > 1 || p.ep_square < -1 || p.ep_square > 63)
       return az::fail_abi(AZ_E_INVALID, "malformed az_chess_pos");
-  AZC_HIP(hipMemcpyAsync(e->tree_roots, r.data(), n * sizeof(az_chess_pos), hipMemcpyHostToDevice, e->stream));
+  AZ_HIP(hipMemcpyAsync(e->tree_roots, r.data(), n * sizeof(az_chess_pos), hipMemcpyHostToDevice, e->stream));
   tree_reset_kernel<<<(n + 63) / 64, 64, 0, e->stream>>>(e->g, e->t, n, e->tree_slots, e->tree_roots);
-  AZC_HIP(hipGetLastError());
-  AZC_HIP(hipStreamSynchronize(e->stream));
+  AZ_HIP(hipGetLastError());
+  AZ_HIP(hipStreamSynchronize(e->stream));
   return 0;
 }
 
 int az_chess_tree_release(az_chess_engine* e, int n, const int32_t* slots) {
   if (!e) return az::fail_abi(AZ_E_INVALID, "null engine");
-  AZC_HIP(hipSetDevice(e->device));
+  AZ_HIP(hipSetDevice(e->device));
   int rc;
   if ((rc = sync_lanes(e)) || (rc = tree_slot_list(e, n, slots))) return rc;
   if (!n) return 0;
   tree_release_kernel<<<(n + 63) / 64, 64, 0, e->stream>>>(e->t, n, e->tree_slots);
-  AZC_HIP(hipGetLastError());
-  AZC_HIP(hipStreamSynchronize(e->stream));
+  AZ_HIP(hipGetLastError());
+  AZ_HIP(hipStreamSynchronize(e->stream));
   return 0;
 }
 
@@ -1759,7 +1636,7 @@ int az_chess_tree_search(az_chess_engine* e, int n_sims) {
   if (!e || n_sims < 0) return az::fail_abi(AZ_E_INVALID, "bad arguments");
   if (e->cfg.evaluator == AZ_EVAL_NETWORK && !e->net.ready)
     return az::fail_abi(AZ_E_STATE, "network evaluator selected but az_chess_engine_set_weights was not called");
-  AZC_HIP(hipSetDevice(e->device));
+  AZ_HIP(hipSetDevice(e->device));
   int rc;
   for (int s = 0; s < n_sims; ++s)
     for (CLane* L : e->lanes)
@@ -1773,15 +1650,15 @@ int az_chess_tree_search(az_chess_engine* e, int n_sims) {
 int az_chess_tree_play(az_chess_engine* e, const double* uniforms, int greedy, int deterministic, int32_t* moves,
                        int32_t* status, int32_t* policy_n, int16_t* policy_actions, double* policy_probs) {
   if (!e || (!deterministic && !uniforms)) return az::fail_abi(AZ_E_INVALID, "bad arguments");
-  AZC_HIP(hipSetDevice(e->device));
+  AZ_HIP(hipSetDevice(e->device));
   int rc;
   if ((rc = sync_lanes(e)) || (rc = tree_buffers(e))) return rc;
   const size_t S = (size_t)e->g.slots, M = AZ_CHESS_MAX_MOVES;
-  if (!deterministic) AZC_HIP(hipMemcpyAsync(e->tree_u, uniforms, S * sizeof(double), hipMemcpyHostToDevice, e->stream));
-  AZC_HIP(hipMemsetAsync(e->tree_move, 0xff, S * sizeof(int32_t), e->stream));
-  AZC_HIP(hipMemsetAsync(e->tree_status, 0, S * sizeof(int32_t), e->stream));
-  AZC_HIP(hipMemsetAsync(e->tree_pol_n, 0, S * sizeof(int32_t), e->stream));
-  AZC_HIP(hipStreamSynchronize(e->stream));
+  if (!deterministic) AZ_HIP(hipMemcpyAsync(e->tree_u, uniforms, S * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  AZ_HIP(hipMemsetAsync(e->tree_move, 0xff, S * sizeof(int32_t), e->stream));
+  AZ_HIP(hipMemsetAsync(e->tree_status, 0, S * sizeof(int32_t), e->stream));
+  AZ_HIP(hipMemsetAsync(e->tree_pol_n, 0, S * sizeof(int32_t), e->stream));
+  AZ_HIP(hipStreamSynchronize(e->stream));
   for (CLane* L : e->lanes) {
     const size_t f = (size_t)L->first;
     CPlayOut po;
@@ -1795,29 +1672,29 @@ int az_chess_tree_play(az_chess_engine* e, const double* uniforms, int greedy, i
     po.pol_p = e->tree_pol_p + f * M;
     play_kernel<<<L->g.slots, 64, 0, L->stream>>>(L->g, L->t, CSamples{}, po);
   }
-  AZC_HIP(hipGetLastError());
+  AZ_HIP(hipGetLastError());
   if ((rc = sync_lanes(e)) || (rc = check_errors(e))) return rc;
-  if (moves) AZC_HIP(hipMemcpy(moves, e->tree_move, S * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (status) AZC_HIP(hipMemcpy(status, e->tree_status, S * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (policy_n) AZC_HIP(hipMemcpy(policy_n, e->tree_pol_n, S * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (policy_actions) AZC_HIP(hipMemcpy(policy_actions, e->tree_pol_a, S * M * sizeof(int16_t), hipMemcpyDeviceToHost));
-  if (policy_probs) AZC_HIP(hipMemcpy(policy_probs, e->tree_pol_p, S * M * sizeof(double), hipMemcpyDeviceToHost));
+  if (moves) AZ_HIP(hipMemcpy(moves, e->tree_move, S * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (status) AZ_HIP(hipMemcpy(status, e->tree_status, S * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (policy_n) AZ_HIP(hipMemcpy(policy_n, e->tree_pol_n, S * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (policy_actions) AZ_HIP(hipMemcpy(policy_actions, e->tree_pol_a, S * M * sizeof(int16_t), hipMemcpyDeviceToHost));
+  if (policy_probs) AZ_HIP(hipMemcpy(policy_probs, e->tree_pol_p, S * M * sizeof(double), hipMemcpyDeviceToHost));
   return 0;
 }
 
 int az_chess_tree_info(az_chess_engine* e, int slot, int64_t* info, float* root_value) {
   if (!e || !info || slot < 0 || slot >= e->g.slots) return az::fail_abi(AZ_E_INVALID, "bad arguments");
-  AZC_HIP(hipSetDevice(e->device));
+  AZ_HIP(hipSetDevice(e->device));
   int rc;
   if ((rc = sync_lanes(e))) return rc;
   int32_t top, first, cnt, ply;
   int64_t gid;
-  AZC_HIP(hipMemcpy(&top, e->t.top + slot, 4, hipMemcpyDeviceToHost));
-  AZC_HIP(hipMemcpy(&first, e->t.root_first + slot, 4, hipMemcpyDeviceToHost));
-  AZC_HIP(hipMemcpy(&cnt, e->t.root_n + slot, 4, hipMemcpyDeviceToHost));
-  AZC_HIP(hipMemcpy(&ply, e->t.ply + slot, 4, hipMemcpyDeviceToHost));
-  AZC_HIP(hipMemcpy(&gid, e->t.game_id + slot, 8, hipMemcpyDeviceToHost));
-  if (root_value) AZC_HIP(hipMemcpy(root_value, e->t.root_value + slot, 4, hipMemcpyDeviceToHost));
+  AZ_HIP(hipMemcpy(&top, e->t.top + slot, 4, hipMemcpyDeviceToHost));
+  AZ_HIP(hipMemcpy(&first, e->t.root_first + slot, 4, hipMemcpyDeviceToHost));
+  AZ_HIP(hipMemcpy(&cnt, e->t.root_n + slot, 4, hipMemcpyDeviceToHost));
+  AZ_HIP(hipMemcpy(&ply, e->t.ply + slot, 4, hipMemcpyDeviceToHost));
+  AZ_HIP(hipMemcpy(&gid, e->t.game_id + slot, 8, hipMemcpyDeviceToHost));
+  if (root_value) AZ_HIP(hipMemcpy(root_value, e->t.root_value + slot, 4, hipMemcpyDeviceToHost));
   info[0] = top;
   info[1] = first;
   info[2] = cnt;
@@ -1829,16 +1706,16 @@ int az_chess_tree_info(az_chess_engine* e, int slot, int64_t* info, float* root_
 int az_chess_tree_export(az_chess_engine* e, int slot, double* prior, double* w, int32_t* n, int32_t* child,
                          int32_t* child_n, int32_t* moves, float* child_value) {
   if (!e || slot < 0 || slot >= e->g.slots) return az::fail_abi(AZ_E_INVALID, "bad arguments");
-  AZC_HIP(hipSetDevice(e->device));
+  AZ_HIP(hipSetDevice(e->device));
   int rc;
   if ((rc = sync_lanes(e))) return rc;
   int32_t top, half;
-  AZC_HIP(hipMemcpy(&top, e->t.top + slot, 4, hipMemcpyDeviceToHost));
-  AZC_HIP(hipMemcpy(&half, e->t.half + slot, 4, hipMemcpyDeviceToHost));
+  AZ_HIP(hipMemcpy(&top, e->t.top + slot, 4, hipMemcpyDeviceToHost));
+  AZ_HIP(hipMemcpy(&half, e->t.half + slot, 4, hipMemcpyDeviceToHost));
   std::vector<az::Edge> h(top);
   if (top)
-    AZC_HIP(hipMemcpy(h.data(), e->t.edges + ((size_t)slot * 2 + half) * e->g.half_cap, top * sizeof(az::Edge),
-                      hipMemcpyDeviceToHost));
+    AZ_HIP(hipMemcpy(h.data(), e->t.edges + ((size_t)slot * 2 + half) * e->g.half_cap, top * sizeof(az::Edge),
+                     hipMemcpyDeviceToHost));
   for (int i = 0; i < top; ++i) {
     if (prior) prior[i] = h[i].prior;
     if (w) w[i] = h[i].W;
@@ -1853,22 +1730,12 @@ int az_chess_tree_export(az_chess_engine* e, int slot, double* prior, double* w,
 
 int az_chess_timer_enable(az_chess_engine* e, int on) {
   if (!e) return az::fail_abi(AZ_E_INVALID, "null engine");
-  AZC_HIP(hipSetDevice(e->device));
-  AZC_HIP(hipStreamSynchronize(e->stream));
-  if (!e->timer_ref) AZC_HIP(hipEventCreate(&e->timer_ref));
-  AZC_HIP(hipEventRecord(e->timer_ref, e->stream));
-  AZC_HIP(hipStreamSynchronize(e->stream));
+  AZ_HIP(hipSetDevice(e->device));
   int rc;
   if ((rc = sync_lanes(e))) return rc;
   std::vector<az::ConvTimer*> timers = {&e->timer};
   for (CLane* L : e->lanes) timers.push_back(&L->timer);
-  for (az::ConvTimer* tm : timers) {
-    tm->flush();
-    tm->reset();
-    tm->ref = &e->timer_ref;
-    tm->enabled = on != 0;
-  }
-  return 0;
+  return az::arm_timers(&e->timer_ref, e->stream, timers, on != 0, 1);
 }
 
 }  // extern "C"

@@ -12,28 +12,13 @@
 #include <vector>
 
 #include "../../include/az.h"
+#include "az_host.h"
 #include "az_nn.h"
 #include "az_tree.h"
 
 namespace {
 
-thread_local std::string g_last_error;
-
-int fail(int code, const std::string& msg) {
-  g_last_error = msg;
-  return code;
-}
-
-#define AZ_HIP(expr)                                                                    \
-  do {                                                                                  \
-    hipError_t err__ = (expr);                                                          \
-    if (err__ != hipSuccess)                                                            \
-      return fail(AZ_E_HIP, std::string(#expr) + ": " + hipGetErrorString(err__));      \
-  } while (0)
-
-// libm pow through a volatile pointer: Python's `int ** 0.5` (mcts.py:50) is
-// float_pow -> pow(n, 0.5), which is NOT sqrt for 1,638 n <= 2e6.
-double (*volatile g_pow)(double, double) = pow;
+constexpr auto& fail = az::fail_abi;
 
 // HIP hardware queues of this process (GPU_MAX_HW_QUEUES, HIP's default 4),
 // read once when the library loads -- HIP reads the variable at its own
@@ -48,11 +33,6 @@ int read_hw_queues() {
 const int g_hw_queues_at_load = read_hw_queues();
 
 }  // namespace
-
-namespace az {
-// error reporting for the other ABI translation units (az_chess.hip)
-int fail_abi(int code, const std::string& msg) { return fail(code, msg); }
-}  // namespace az
 
 // A lane = a contiguous group of slots searched on its own HIP stream.  Lanes
 // share the network, the transposition cache, the sample sink and the
@@ -73,7 +53,6 @@ struct Lane {
   float* values = nullptr;
   az::ConvTimer timer;
   az::ConvTimer tree_timer;  // select and expand launches (bench.py roofline_tree)
-  hipEvent_t move_done[4] = {nullptr, nullptr, nullptr, nullptr};  // end of move m on this lane, m mod 4
   int64_t pool_cap = 0;        // compacted self-play: edges per pool half (TreeDev::pool_cap)
 };
 
@@ -105,68 +84,33 @@ struct az_engine {
   size_t noise_cap = 0;
   int32_t* dev_i32 = nullptr;  // scratch for az_tree_reset
   az::Board* dev_boards = nullptr;
-  std::vector<void*> owned;
-  std::vector<void*> sample_bufs;
+  az::DeviceAllocs mem;
+  az::DeviceAllocs samples;  // the self-play sample buffers, re-made at every az_selfplay_begin
   std::vector<hipStream_t> lane_streams;
   hipEvent_t timer_ref = nullptr;  // common origin of every ConvTimer's intervals
   int64_t sp_first = 0, sp_n = 0;
-  int64_t moves_issued = 0;        // self-play moves enqueued (lane drift bound, az_tree.h)
   uint32_t leaf_epoch = 0;         // simulations enqueued, every lane's (TreeDev::leaf_epoch)
-  int64_t drained = 0;             // finished games az_selfplay_drain has returned
   uint8_t* drain_dev = nullptr;    // packed records (device) and their pinned host copy
   uint8_t* drain_host = nullptr;
-  // games-finished count at the end of every move: the last lane to finish
-  // move m stores smp.done_count into snap_host[m % 4] (move_end_kernel), and
-  // the drain packs up to a completed snapshot on pack_stream, so it never
-  // waits for the move that is running (az_selfplay_step without stats returns
-  // without a sync).  No stream of its own: HIP maps streams onto 4 hardware
-  // queues per process (GPU_MAX_HW_QUEUES), and a snapshot or pack stream
-  // sharing a lane's queue runs behind that lane's queued moves -- with two
-  // lanes the pack uses `stream`, idle while moves run.
+  // the drain packs up to a completed snapshot of the clock on pack_stream.
+  // No stream of its own: HIP maps streams onto 4 hardware queues per process
+  // (GPU_MAX_HW_QUEUES), and a snapshot or pack stream sharing a lane's queue
+  // runs behind that lane's queued moves -- with two lanes the pack uses
+  // `stream`, idle while moves run.
+  az::MoveClock clock;
   hipStream_t pack_stream = nullptr;
   bool own_pack_stream = false;
-  int32_t* move_arrive = nullptr;           // [4] lanes done with move m, slot m % 4
-  unsigned long long* snap_host = nullptr;  // [4] pinned coherent, move m in slot m % 4
-  unsigned long long* snap_dev = nullptr;   // snap_host's device address
-  int64_t batch_first_move = 0;             // moves_issued at az_selfplay_begin
   size_t drain_cap = 0;            // records the two buffers hold
   // a host evaluator failed mid-simulation (AZ_E_CALLBACK): the leaves it
   // selected were never expanded, so the trees are one simulation short;
   // searching refuses until az_selfplay_begin or az_tree_reset starts over
   bool broken = false;
-
-  template <typename T>
-  int alloc(T** p, size_t count) {
-    void* q = nullptr;
-    AZ_HIP(hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T)));
-    owned.push_back(q);
-    *p = reinterpret_cast<T*>(q);
-    return 0;
-  }
 };
 
 namespace {
 
 int check_device_errors(az_engine* e) {
-  unsigned long long err = 0;
-  AZ_HIP(hipMemcpy(&err, e->t.stats + az::kStatErrors, sizeof(err), hipMemcpyDeviceToHost));
-  if (err) {
-    std::string m = "device error flags:";
-    if (err & az::kErrArena) m += " arena-overflow(raise az_config.arena_edges)";
-    if (err & az::kErrPow) m += " visit-table-overflow(raise az_config.max_tree_visits)";
-    if (err & az::kErrPath) m += " path-overflow";
-    if (err & az::kErrIllegal) m += " illegal-move";
-    if (err & az::kErrNoRoot) m += " play-before-search";
-    if (err & az::kErrNoise) m += " root-noise-rows-exhausted(pass a row per root selection)";
-    if (err & az::kErrActRange)
-      m += " activation-range(a non-finite activation, or |x| > 32752 in the per-layer fp16x2 convs: "
-           "use conv_algo=AZ_CONV_F16X2 or AZ_CONV_DIRECT)";
-    // play on a slot without a searched root changes nothing: that flag is
-    // cleared once reported (the others mean a broken tree and stay)
-    if (err == az::kErrNoRoot) AZ_HIP(hipMemset(e->t.stats + az::kStatErrors, 0, sizeof(err)));
-    return fail(AZ_E_DEVICE, m);
-  }
-  return 0;
+  return az::device_error_status(e->t.stats, {"(raise az_config.arena_edges)", "(raise az_config.max_tree_visits)"});
 }
 
 az::Board board_from_cells(const int8_t* cells, int HW) {
@@ -370,27 +314,26 @@ int ready_to_search(az_engine* e) {
 
 // conv16_kernel pack (az_conv16.hip) of a folded 3x3 conv [3][3][cin][F] (+ the
 // 1x1 residual [F][F]): fp16 bits, uploaded as raw storage; *scale = 2^(e-12)
-[[maybe_unused]] int upload_conv16(std::vector<void*>& owned, uint16_t** dst, float* scale,
+// a host array into device memory that `owned` frees
+template <typename T>
+int upload_new(az::DeviceAllocs& owned, T** dst, const std::vector<T>& src) {
+  AZ_TRY(owned.alloc(dst, src.size(), false));
+  AZ_HIP(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+  return 0;
+}
+
+[[maybe_unused]] int upload_conv16(az::DeviceAllocs& owned, uint16_t** dst, float* scale,
                                    const std::vector<double>& w3, int cin, const std::vector<double>* wr) {
   const int e = az::conv16_prescale(w3.data(), w3.size(), wr ? wr->data() : nullptr, wr ? wr->size() : 0);
   std::vector<uint16_t> pack;
   az::conv16_pack(w3.data(), cin, wr ? wr->data() : nullptr, e, pack);
   *scale = std::ldexp(1.f, e - 12);
-  void* q = nullptr;
-  AZ_HIP(hipMalloc(&q, pack.size() * sizeof(uint16_t)));
-  owned.push_back(q);
-  *dst = reinterpret_cast<uint16_t*>(q);
-  AZ_HIP(hipMemcpy(q, pack.data(), pack.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-  return 0;
+  return upload_new(owned, dst, pack);
 }
 
-[[maybe_unused]] int upload(std::vector<void*>& owned, float** dst, const std::vector<float>& src) {
-  if (!*dst) {
-    void* q = nullptr;
-    AZ_HIP(hipMalloc(&q, std::max<size_t>(src.size(), 1) * sizeof(float)));
-    owned.push_back(q);
-    *dst = reinterpret_cast<float*>(q);
-  }
+// (a set tensor keeps its buffer: az_engine_set_weights again)
+[[maybe_unused]] int upload(az::DeviceAllocs& owned, float** dst, const std::vector<float>& src) {
+  if (!*dst) AZ_TRY(owned.alloc(dst, src.size(), false));
   AZ_HIP(hipMemcpy(*dst, src.data(), src.size() * sizeof(float), hipMemcpyHostToDevice));
   return 0;
 }
@@ -429,7 +372,7 @@ int make_lane(az_engine* e, Lane* L, int first, int n, bool own_queue) {
   t.last_policy += f * g.A;
   if (own_queue) {
     int rc;
-    if ((rc = e->alloc(&t.eval_count, az::kCountWords))) return rc;
+    if ((rc = e->mem.alloc(&t.eval_count, az::kCountWords, false))) return rc;
     AZ_HIP(hipMemset(t.eval_count, 0, az::kCountWords * sizeof(int32_t)));
     set_counts(t, t.eval_count, 0);
     t.epoch = 0;
@@ -448,7 +391,7 @@ int alloc_pool(az_engine* e, Lane* L, int64_t cap) {
   int rc;
   az::Edge* halves = nullptr;
   unsigned long long* tops = nullptr;
-  if ((rc = e->alloc(&halves, 2 * (size_t)cap)) || (rc = e->alloc(&tops, 2))) return rc;
+  if ((rc = e->mem.alloc(&halves, 2 * (size_t)cap, false)) || (rc = e->mem.alloc(&tops, 2, false))) return rc;
   AZ_HIP(hipMemset(tops, 0, 2 * sizeof(unsigned long long)));
   L->pool_cap = cap;
   L->t.pool_cap = (int32_t)cap;
@@ -468,7 +411,7 @@ namespace az {
 // small-weight blob); in_ch > 4 (chess, 118 planes): the stem is one more
 // conv16 3x3 conv over the input zero-padded to F channels (stem_k).
 int load_network(NetDev& net, const az_tensor* tensors, int n, int in_ch, int HW, int A, double eps,
-                 std::vector<void*>& owned) {
+                 DeviceAllocs& owned) {
   std::map<std::string, const az_tensor*> m;
   for (int i = 0; i < n; ++i) {
     if (!tensors[i].name || !tensors[i].data) return fail(AZ_E_INVALID, "tensor without name/data");
@@ -492,11 +435,7 @@ int load_network(NetDev& net, const az_tensor* tensors, int n, int in_ch, int HW
     std::vector<uint16_t> pack;
     tower16_stem_pack(w.data(), e, pack);
     stem_s = std::ldexp(1.f, e - 12);
-    void* q = nullptr;
-    AZ_HIP(hipMalloc(&q, pack.size() * sizeof(uint16_t)));
-    owned.push_back(q);
-    stem16 = reinterpret_cast<uint16_t*>(q);
-    AZ_HIP(hipMemcpy(q, pack.data(), pack.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    if ((rc = upload_new(owned, &stem16, pack))) return rc;
   }
   {
     std::vector<float> bs(F);
@@ -671,11 +610,9 @@ int load_network(NetDev& net, const az_tensor* tensors, int n, int in_ch, int HW
       tn.skip[0] = skip[0];
       tn.skip[1] = skip[1];
       if (!pix.empty()) {
-        void* q = nullptr;
-        AZ_HIP(hipMalloc(&q, pix.size() * sizeof(int)));
-        owned.push_back(q);
-        AZ_HIP(hipMemcpy(q, pix.data(), pix.size() * sizeof(int), hipMemcpyHostToDevice));
-        tn.slot_pix = reinterpret_cast<const int*>(q);
+        int* q = nullptr;
+        if ((rc = upload_new(owned, &q, pix))) return rc;
+        tn.slot_pix = q;
       }
     }
     // dual launches (tower16_dual_kernel): boards of 33-48 cells (Connect-4)
@@ -712,26 +649,17 @@ int load_network(NetDev& net, const az_tensor* tensors, int n, int in_ch, int HW
       tn.alt_skip[0] = skip[0];
       tn.alt_skip[1] = skip[1];
       if (!pix.empty()) {
-        void* q = nullptr;
-        AZ_HIP(hipMalloc(&q, pix.size() * sizeof(int)));
-        owned.push_back(q);
-        AZ_HIP(hipMemcpy(q, pix.data(), pix.size() * sizeof(int), hipMemcpyHostToDevice));
-        tn.alt_slot_pix = reinterpret_cast<const int*>(q);
+        int* q = nullptr;
+        if ((rc = upload_new(owned, &q, pix))) return rc;
+        tn.alt_slot_pix = q;
       }
     }
     tn.depth = net.depth;
     tn.hidden = net.hidden;
-    if (!net.tower) {
-      void* q = nullptr;
-      AZ_HIP(hipMalloc(&q, sizeof(TowerNet)));
-      owned.push_back(q);
-      net.tower = reinterpret_cast<TowerNet*>(q);
-    }
-    void* qb = nullptr;
-    AZ_HIP(hipMalloc(&qb, blob.size() * sizeof(float)));
-    owned.push_back(qb);
-    AZ_HIP(hipMemcpy(qb, blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice));
-    tn.blob = reinterpret_cast<const float*>(qb);
+    if (!net.tower && (rc = owned.alloc(&net.tower, 1, false))) return rc;
+    float* qb = nullptr;
+    if ((rc = upload_new(owned, &qb, blob))) return rc;
+    tn.blob = qb;
     AZ_HIP(hipMemcpy(net.tower, &tn, sizeof(TowerNet), hipMemcpyHostToDevice));
     net.tower_staged = tn.staged_floats;
     net.tower_dbuf = tn.dbuf != 0;
@@ -760,7 +688,7 @@ int az_abi_version(void) { return AZ_ABI_VERSION; }
 #endif
 const char* az_build_id(void) { return AZ_SRC_HASH; }
 const char* az_build_flags(void) { return AZ_BUILD_EXTRA; }
-const char* az_last_error(void) { return g_last_error.c_str(); }
+const char* az_last_error(void) { return az::g_last_error.c_str(); }
 
 int az_engine_create(int device, const az_config* cfg, az_engine** out) {
   if (!cfg || !out) return fail(AZ_E_INVALID, "null argument");
@@ -783,11 +711,7 @@ int az_engine_create(int device, const az_config* cfg, az_engine** out) {
     return fail(AZ_E_INVALID, "unknown evaluator");
   if (c.evaluator == AZ_EVAL_NETWORK && c.filters != 128)
     return fail(AZ_E_INVALID, "network evaluator supports filters == 128 (ConfigModel.filters)");
-  int dev_count = 0;
-  if (hipGetDeviceCount(&dev_count) != hipSuccess || dev_count == 0)
-    return fail(AZ_E_HIP, "no HIP device visible: libaz has no CPU fallback");
-  if (device < 0 || device >= dev_count) return fail(AZ_E_INVALID, "bad device index");
-  AZ_HIP(hipSetDevice(device));
+  AZ_TRY(az::open_device(device));
 
   az_engine* e = new az_engine();
   e->device = device;
@@ -859,25 +783,24 @@ int az_engine_create(int device, const az_config* cfg, az_engine** out) {
   az::TreeDev& t = e->t;
   t.edges = nullptr;
   t.arena_end = t.slot_live = nullptr;
-  if (g.halves == 1 && (rc = e->alloc(&t.edges, S * (size_t)g.arena_cap))) return cleanup(rc);
-  if (g.halves > 1 && ((rc = e->alloc(&t.arena_end, S)) || (rc = e->alloc(&t.slot_live, S)))) return cleanup(rc);
-  if ((rc = e->alloc(&t.root_board, S)) ||
-      (rc = e->alloc(&t.root_first, S)) || (rc = e->alloc(&t.root_n, S)) ||
-      (rc = e->alloc(&t.root_value, S)) || (rc = e->alloc(&t.arena_top, S)) ||
-      (rc = e->alloc(&t.ply, S)) || (rc = e->alloc(&t.game_id, S)) ||
-      (rc = e->alloc(&t.path, S * g.max_depth)) || (rc = e->alloc(&t.path_len, S)) ||
-      (rc = e->alloc(&t.slot_expansions, S)) || (rc = e->alloc(&t.mt, S * (az::kMtN + 1))) ||
-      (rc = e->alloc(&t.leaf_src, S)) || (rc = e->alloc(&t.leaf_board, S)) ||
-      (rc = e->alloc(&t.eval_board, S)) || (rc = e->alloc(&t.nn_board, S)) ||
-      (rc = e->alloc(&t.eval_count, az::kCountWords)) || (rc = e->alloc(&t.stats, az::kStatCount)) ||
-      (rc = e->alloc(&t.last_move, S)) || (rc = e->alloc(&t.last_status, S)) ||
-      (rc = e->alloc(&t.last_policy, S * A)))
+  if (g.halves == 1 && (rc = e->mem.alloc(&t.edges, S * (size_t)g.arena_cap, false))) return cleanup(rc);
+  if (g.halves > 1 && ((rc = e->mem.alloc(&t.arena_end, S, false)) || (rc = e->mem.alloc(&t.slot_live, S, false)))) return cleanup(rc);
+  if ((rc = e->mem.alloc(&t.root_board, S, false)) ||
+      (rc = e->mem.alloc(&t.root_first, S, false)) || (rc = e->mem.alloc(&t.root_n, S, false)) ||
+      (rc = e->mem.alloc(&t.root_value, S, false)) || (rc = e->mem.alloc(&t.arena_top, S, false)) ||
+      (rc = e->mem.alloc(&t.ply, S, false)) || (rc = e->mem.alloc(&t.game_id, S, false)) ||
+      (rc = e->mem.alloc(&t.path, S * g.max_depth, false)) || (rc = e->mem.alloc(&t.path_len, S, false)) ||
+      (rc = e->mem.alloc(&t.slot_expansions, S, false)) || (rc = e->mem.alloc(&t.mt, S * (az::kMtN + 1), false)) ||
+      (rc = e->mem.alloc(&t.leaf_src, S, false)) || (rc = e->mem.alloc(&t.leaf_board, S, false)) ||
+      (rc = e->mem.alloc(&t.eval_board, S, false)) || (rc = e->mem.alloc(&t.nn_board, S, false)) ||
+      (rc = e->mem.alloc(&t.eval_count, az::kCountWords, false)) || (rc = e->mem.alloc(&t.stats, az::kStatCount, false)) ||
+      (rc = e->mem.alloc(&t.last_move, S, false)) || (rc = e->mem.alloc(&t.last_status, S, false)) ||
+      (rc = e->mem.alloc(&t.last_policy, S * A, false)))
     return cleanup(rc);
   double* powtab = nullptr;
-  if ((rc = e->alloc(&powtab, g.pow_len))) return cleanup(rc);
+  if ((rc = e->mem.alloc(&powtab, g.pow_len, false))) return cleanup(rc);
   {
-    std::vector<double> h(g.pow_len);
-    for (int k = 0; k < g.pow_len; ++k) h[k] = k == 0 ? 0.0 : g_pow((double)k, 0.5);
+    const std::vector<double> h = az::sqrt_pow_table(g.pow_len);
     if (hipMemcpy(powtab, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
       return cleanup(fail(AZ_E_HIP, "pow table upload failed"));
   }
@@ -893,8 +816,8 @@ int az_engine_create(int device, const az_config* cfg, az_engine** out) {
   if (c.cache_log2 > 0) {
     const size_t cap = (size_t)1 << c.cache_log2;
     az::CacheDev& cd = e->cache;
-    if ((rc = e->alloc(&cd.keys, cap)) || (rc = e->alloc(&cd.state, cap)) ||
-        (rc = e->alloc(&cd.pay, cap * (A + 1))) || (rc = e->alloc(&cd.ctl, 4)))
+    if ((rc = e->mem.alloc(&cd.keys, cap, false)) || (rc = e->mem.alloc(&cd.state, cap, false)) ||
+        (rc = e->mem.alloc(&cd.pay, cap * (A + 1), false)) || (rc = e->mem.alloc(&cd.ctl, 4, false)))
       return cleanup(rc);
     cd.mask = (uint32_t)(cap - 1);
     cd.enabled = 1;
@@ -917,11 +840,11 @@ int az_engine_create(int device, const az_config* cfg, az_engine** out) {
       hipMemset(t.game_id, 0xff, S * sizeof(int64_t)) != hipSuccess)
     return cleanup(fail(AZ_E_HIP, "memset failed"));
   // evaluator buffers (batch = slots)
-  if ((rc = e->alloc(&e->probs, S * A)) || (rc = e->alloc(&e->values, S)) ||
-      (rc = e->alloc(&e->uniforms, S)) || (rc = e->alloc(&e->dev_i32, S)) ||
-      (rc = e->alloc(&e->dev_boards, S)))
+  if ((rc = e->mem.alloc(&e->probs, S * A, false)) || (rc = e->mem.alloc(&e->values, S, false)) ||
+      (rc = e->mem.alloc(&e->uniforms, S, false)) || (rc = e->mem.alloc(&e->dev_i32, S, false)) ||
+      (rc = e->mem.alloc(&e->dev_boards, S, false)))
     return cleanup(rc);
-  if ((rc = e->alloc(&e->x, S * g.HW * 4))) return cleanup(rc);
+  if ((rc = e->mem.alloc(&e->x, S * g.HW * 4, false))) return cleanup(rc);
   if (c.evaluator == AZ_EVAL_HOST) {
     if (hipHostMalloc(&e->host_x, (size_t)S * g.HW * 4 * sizeof(float), hipHostMallocDefault) != hipSuccess ||
         hipHostMalloc(&e->host_p, (size_t)S * A * sizeof(float), hipHostMallocDefault) != hipSuccess ||
@@ -932,7 +855,7 @@ int az_engine_create(int device, const az_config* cfg, az_engine** out) {
   if (c.evaluator == AZ_EVAL_NETWORK) {
     const size_t act = S * g.HW * 128;
     for (int i = 0; i < 3; ++i)
-      if ((rc = e->alloc(&e->act[i], act))) return cleanup(rc);
+      if ((rc = e->mem.alloc(&e->act[i], act, false))) return cleanup(rc);
   }
   e->net.depth = c.depth;
   e->net.board_h = g.H;
@@ -974,9 +897,6 @@ int az_engine_create(int device, const az_config* cfg, az_engine** out) {
         return cleanup(fail(AZ_E_HIP, "hipStreamCreate failed"));
       e->lane_streams.push_back(st);
       L->stream = st;
-      for (hipEvent_t& ev : L->move_done)
-        if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess)
-          return cleanup(fail(AZ_E_HIP, "hipEventCreate failed"));
     }
   }
   e->net.lanes = (int)e->lanes.size();  // (the tower's dual-launch threshold, load_network)
@@ -984,10 +904,6 @@ int az_engine_create(int device, const az_config* cfg, az_engine** out) {
     for (Lane* L : e->lanes)
       if ((rc = alloc_pool(e, L, std::min<int64_t>((int64_t)g.arena_cap * L->n, (1ll << 31) - 1))))
         return cleanup(rc);
-  if (nl == 1)
-    for (hipEvent_t& ev : e->whole.move_done)
-      if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess)
-        return cleanup(fail(AZ_E_HIP, "hipEventCreate failed"));
   // drain: one lane runs on `stream`, so the pack needs a stream of its own;
   // with more lanes `stream` is idle while moves run
   e->own_pack_stream = nl == 1;
@@ -997,12 +913,7 @@ int az_engine_create(int device, const az_config* cfg, az_engine** out) {
   } else {
     e->pack_stream = e->stream;
   }
-  if ((rc = e->alloc(&e->move_arrive, 4))) return cleanup(rc);
-  if (hipMemset(e->move_arrive, 0, 4 * sizeof(int32_t)) != hipSuccess ||
-      hipHostMalloc(&e->snap_host, 4 * sizeof(unsigned long long), hipHostMallocCoherent) != hipSuccess ||
-      hipHostGetDevicePointer((void**)&e->snap_dev, e->snap_host, 0) != hipSuccess)
-    return cleanup(fail(AZ_E_HIP, "drain snapshot setup failed"));
-  for (int i = 0; i < 4; ++i) e->snap_host[i] = 0;
+  if ((rc = e->clock.create(e->mem, nl, "drain snapshot setup failed"))) return cleanup(rc);
   e->net.hidden = c.value_hidden;
   *out = e;
   return 0;
@@ -1022,19 +933,13 @@ int az_engine_destroy(az_engine* eng) {
     (void)hipStreamSynchronize(eng->pack_stream);
     (void)hipStreamDestroy(eng->pack_stream);
   }
-  if (eng->snap_host) (void)hipHostFree(eng->snap_host);
-  for (Lane* L : eng->lanes) {
-    for (hipEvent_t ev : L->move_done)
-      if (ev) (void)hipEventDestroy(ev);
+  eng->clock.destroy();
+  for (Lane* L : eng->lanes)
     if (L != &eng->whole) delete L;
-  }
-  if (eng->lanes.size() > 1)
-    for (hipEvent_t ev : eng->whole.move_done)
-      if (ev) (void)hipEventDestroy(ev);
   if (eng->drain_dev) (void)hipFree(eng->drain_dev);
   if (eng->drain_host) (void)hipHostFree(eng->drain_host);
-  for (void* p : eng->sample_bufs) (void)hipFree(p);
-  for (void* p : eng->owned) (void)hipFree(p);
+  eng->samples.free_all();
+  eng->mem.free_all();
   if (eng->timer_ref) (void)hipEventDestroy(eng->timer_ref);
   for (void* q : {(void*)eng->host_x, (void*)eng->host_p, (void*)eng->host_v, (void*)eng->host_n})
     if (q) (void)hipHostFree(q);
@@ -1056,7 +961,7 @@ int az_engine_set_weights(az_engine* e, const az_tensor* tensors, int n) {
   if (!e || (!tensors && n)) return fail(AZ_E_INVALID, "null argument");
   if (int rc_ = enter(e)) return rc_;
   int rc;
-  if ((rc = az::load_network(e->net, tensors, n, 4, e->g.HW, e->g.A, e->cfg.bn_epsilon, e->owned)))
+  if ((rc = az::load_network(e->net, tensors, n, 4, e->g.HW, e->g.A, e->cfg.bn_epsilon, e->mem)))
     return rc;
   return cache_clear(e);  // cached outputs belong to the previous weights
 }
@@ -1113,40 +1018,13 @@ int az_stats_get(az_engine* e, az_stats* st) {
   int rc;
   if ((rc = sync_all(e))) return rc;
   unsigned long long h[az::kStatCount];
-  AZ_HIP(hipMemcpy(h, e->t.stats, sizeof(h), hipMemcpyDeviceToHost));
-  std::vector<int64_t> gid(e->g.slots);
-  AZ_HIP(hipMemcpy(gid.data(), e->t.game_id, gid.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
-  memset(st, 0, sizeof(*st));
-  st->expansions = (int64_t)h[az::kStatExpansions];
-  st->terminal_visits = (int64_t)h[az::kStatTerminal];
-  st->games_done = (int64_t)h[az::kStatGamesDone];
-  st->simulations = (int64_t)h[az::kStatSims];
-  st->plies = (int64_t)h[az::kStatPlies];
-  st->errors = (int64_t)h[az::kStatErrors];
-  st->active_slots = std::count_if(gid.begin(), gid.end(), [](int64_t v) { return v >= 0; });
+  if ((rc = az::read_common_stats(st, h, e->t.stats, e->t.game_id, e->g.slots, e->cache.ctl, e->cache.gen_size,
+                                  e->cache.mask)))
+    return rc;
   std::vector<az::ConvTimer*> timers = {&e->timer, &e->whole.timer};
   for (Lane* L : e->lanes)
     if (L != &e->whole) timers.push_back(&L->timer);
-  std::vector<std::pair<double, double>> iv;
-  for (az::ConvTimer* tm : timers) {
-    tm->flush();
-    st->conv_ms += tm->total_ms;
-    st->conv_launches += tm->launches;
-    iv.insert(iv.end(), tm->intervals.begin(), tm->intervals.end());
-  }
-  std::sort(iv.begin(), iv.end());
-  double busy = 0.0, lo = 0.0, hi = -1.0;
-  for (const auto& x : iv) {
-    if (x.first > hi) {
-      if (hi > lo) busy += hi - lo;
-      lo = x.first;
-      hi = x.second;
-    } else {
-      hi = std::max(hi, x.second);
-    }
-  }
-  if (hi > lo) busy += hi - lo;
-  st->conv_busy_ms = busy;
+  az::conv_busy_union(timers, st);
   std::vector<az::ConvTimer*> ttimers = {&e->whole.tree_timer};
   for (Lane* L : e->lanes)
     if (L != &e->whole) ttimers.push_back(&L->tree_timer);
@@ -1157,18 +1035,7 @@ int az_stats_get(az_engine* e, az_stats* st) {
   }
   st->path_edges = (int64_t)h[az::kStatPathEdges];
   st->max_retained = (int64_t)h[az::kStatMaxRetained];
-  st->cache_hits = (int64_t)h[az::kStatCacheHits];
-  st->evaluations = (int64_t)h[az::kStatNNEvals];
-  if (e->cache.ctl) {
-    unsigned long long ctl[3];
-    AZ_HIP(hipMemcpy(ctl, e->cache.ctl, sizeof(ctl), hipMemcpyDeviceToHost));
-    st->cache_generation = (int64_t)ctl[0];
-    st->cache_inserts = (int64_t)ctl[1];
-    st->cache_gen_size = (int64_t)e->cache.gen_size;
-    st->cache_entries = (int64_t)ctl[2];
-    st->cache_capacity = (int64_t)e->cache.mask + 1;
-  }
-  st->games_drained = e->drained;
+  st->games_drained = e->clock.drained;
   st->arena_edges = e->g.arena_cap;
   if (e->g.halves > 1) {
     st->arena_pool_edges = 0;
@@ -1200,9 +1067,6 @@ int az_timer_enable(az_engine* e, int on) {
   if (!e) return fail(AZ_E_INVALID, "null engine");
   int rc;
   if ((rc = sync_all(e))) return rc;
-  if (!e->timer_ref) AZ_HIP(hipEventCreate(&e->timer_ref));
-  AZ_HIP(hipEventRecord(e->timer_ref, e->stream));
-  AZ_HIP(hipStreamSynchronize(e->stream));
   // on: 1 = conv launches, 2 = conv + select/expand launches (more events per
   // simulation: bench.py times the tree kernels in a window of their own),
   // k >= 3 = every k-th conv launch of each lane (sampled)
@@ -1212,20 +1076,9 @@ int az_timer_enable(az_engine* e, int on) {
       timers.push_back(&L->timer);
       ttimers.push_back(&L->tree_timer);
     }
-  for (az::ConvTimer* tm : timers) {
-    tm->flush();
-    tm->reset();
-    tm->ref = &e->timer_ref;
-    tm->enabled = on != 0;
-    tm->stride = on >= 3 ? on : 1;
-  }
-  for (az::ConvTimer* tm : ttimers) {
-    tm->flush();
-    tm->reset();
-    tm->ref = &e->timer_ref;
-    tm->enabled = on >= 2;
-  }
-  return 0;
+  // (both lists share the origin; the second call records it again, on streams still idle)
+  AZ_TRY(az::arm_timers(&e->timer_ref, e->stream, timers, on != 0, on >= 3 ? on : 1));
+  return az::arm_timers(&e->timer_ref, e->stream, ttimers, on >= 2, 1);
 }
 
 int az_pow_table(az_engine* e, double* out, int64_t n) {
@@ -1242,31 +1095,21 @@ int az_selfplay_begin(az_engine* e, int64_t first_game, int64_t n_games, uint32_
   if ((rc = ready_to_search(e))) return rc;
   AZ_HIP(hipSetDevice(e->device));
   if ((rc = sync_all(e))) return rc;  // moves of an earlier batch may still be running (async steps)
-  for (void* p : e->sample_bufs) (void)hipFree(p);
-  e->sample_bufs.clear();
+  e->samples.free_all();
   az::SampleDev& smp = e->smp;
   smp = az::SampleDev{};
   smp.first_game = first_game;
   smp.n_games = n_games;
   smp.base_seed = base_seed;
   const size_t G = (size_t)std::max<int64_t>(n_games, 1), P = (size_t)e->g.HW, A = (size_t)e->g.A;
-  auto get = [&](void** p, size_t bytes) -> int {
-    AZ_HIP(hipMalloc(p, std::max<size_t>(bytes, 16)));
-    e->sample_bufs.push_back(*p);
-    AZ_HIP(hipMemsetAsync(*p, 0, std::max<size_t>(bytes, 16), e->stream));
-    return 0;
-  };
-  if ((rc = get((void**)&smp.boards, G * P * sizeof(az::Board))) ||
-      (rc = get((void**)&smp.policy, G * P * A * sizeof(double))) ||
-      (rc = get((void**)&smp.moves, G * P * sizeof(int16_t))) ||
-      (rc = get((void**)&smp.length, G * sizeof(int32_t))) ||
-      (rc = get((void**)&smp.result, G * sizeof(int32_t))) ||
-      (rc = get((void**)&smp.expansions, G * sizeof(int32_t))) ||
-      (rc = get((void**)&smp.done_ids, G * sizeof(int64_t))) ||
-      (rc = get((void**)&smp.done_count, sizeof(unsigned long long))))
+  az::DeviceAllocs& sb = e->samples;
+  hipStream_t s = e->stream;
+  if ((rc = sb.alloc_zeroed_async(&smp.boards, G * P, s)) || (rc = sb.alloc_zeroed_async(&smp.policy, G * P * A, s)) ||
+      (rc = sb.alloc_zeroed_async(&smp.moves, G * P, s)) || (rc = sb.alloc_zeroed_async(&smp.length, G, s)) ||
+      (rc = sb.alloc_zeroed_async(&smp.result, G, s)) || (rc = sb.alloc_zeroed_async(&smp.expansions, G, s)) ||
+      (rc = sb.alloc_zeroed_async(&smp.done_ids, G, s)) || (rc = sb.alloc_zeroed_async(&smp.done_count, 1, s)))
     return rc;
-  e->drained = 0;
-  e->batch_first_move = e->moves_issued;
+  e->clock.begin_batch();
   unsigned long long st[az::kStatCount] = {0};
   const int64_t first_wave = std::min<int64_t>(n_games, e->g.slots);
   st[az::kStatNextGame] = (unsigned long long)(first_game + first_wave);
@@ -1289,30 +1132,22 @@ int az_selfplay_step(az_engine* e, int n_moves, az_stats* st) {
   int rc;
   if ((rc = ready_to_search(e))) return rc;
   AZ_HIP(hipSetDevice(e->device));
-  const bool multi = e->lanes.size() > 1;
   for (int mv = 0; mv < n_moves; ++mv) {
-    const int64_t m = e->moves_issued++;
+    const int64_t m = e->clock.issued++;
     // lanes interleaved per simulation so every stream always has work queued
     for (int s = 0; s < e->g.sims; ++s)
       for (Lane* L : e->lanes)
         if ((rc = simulate(e, *L))) return rc;
-    for (Lane* L : e->lanes) {
-      // a lane plays move m once every other lane has finished move m - 1, so
-      // move m - 1's snapshot (taken by the last of them) holds no game of
-      // move m; it also keeps the lanes within two moves of each other (the
-      // cache eviction bound, az_tree.h)
-      if (multi && m > e->batch_first_move)
-        for (Lane* O : e->lanes)
-          if (O != L) AZ_HIP(hipStreamWaitEvent(L->stream, O->move_done[(m - 1) % 4], 0));
+    for (size_t l = 0; l < e->lanes.size(); ++l) {
+      Lane* L = e->lanes[l];
+      if ((rc = e->clock.before_play(m, l, L->stream))) return rc;
       az::launch_play(L->g, L->t, e->smp, nullptr, -1, 0, 1, L->stream);
       az::launch_compact(L->g, L->t, L->stream);
       if (L->g.halves > 1) {  // the kept trees are in the other half now: it is the current one
         std::swap(L->t.edges, L->t.dst_edges);
         std::swap(L->t.pool_top, L->t.dst_top);
       }
-      az::launch_move_end(e->move_arrive + m % 4, (int)e->lanes.size(), e->smp.done_count,
-                          e->snap_dev + m % 4, L->stream);
-      AZ_HIP(hipEventRecord(L->move_done[m % 4], L->stream));
+      if ((rc = e->clock.after_play(m, l, L->stream, e->smp.done_count))) return rc;
     }
     AZ_HIP(hipGetLastError());
   }
@@ -1367,23 +1202,8 @@ int az_selfplay_drain(az_engine* e, int64_t max_games, int64_t* n_out, int64_t* 
   *n_out = 0;
   if (!e->smp.done_count) return 0;  // no self-play batch begun
   AZ_HIP(hipSetDevice(e->device));
-  // the newest move whose count snapshot is complete; if the last issued
-  // move is still running, wait for the one before it (never for the running one)
-  // (a move's snapshot is complete once every lane has finished the move)
-  const int64_t last = e->moves_issued - 1;
-  int64_t k = -1;
-  bool last_done = last >= e->batch_first_move;
-  if (last_done)
-    for (Lane* L : e->lanes) last_done = last_done && hipEventQuery(L->move_done[last % 4]) == hipSuccess;
-  if (last_done) {
-    k = last;
-  } else if (last - 1 >= e->batch_first_move) {
-    k = last - 1;
-    for (Lane* L : e->lanes) AZ_HIP(hipEventSynchronize(L->move_done[k % 4]));
-  }
-  if (k < 0) return 0;
-  const unsigned long long done = __atomic_load_n(e->snap_host + k % 4, __ATOMIC_ACQUIRE);
-  const int64_t n = std::min<int64_t>((int64_t)done - e->drained, max_games);
+  int64_t n = 0;
+  if (int rc = e->clock.drainable(max_games, &n)) return rc;
   if (n <= 0) return 0;
   const size_t rec = az::drain_record_bytes(e->g);
   if ((size_t)n > e->drain_cap) {
@@ -1397,9 +1217,9 @@ int az_selfplay_drain(az_engine* e, int64_t max_games, int64_t* n_out, int64_t* 
     AZ_HIP(hipHostMalloc(&e->drain_host, cap * rec, hipHostMallocDefault));
     e->drain_cap = cap;
   }
-  // pack_stream (nothing else queued on it; the host has seen move k finish
-  // on every lane): games up to move k are complete
-  az::launch_drain_pack(e->g, e->smp, e->drained, (int)n, e->drain_dev, e->pack_stream);
+  // pack_stream (nothing else queued on it; the host has seen the snapshot's
+  // move finish on every lane): the games it counts are complete
+  az::launch_drain_pack(e->g, e->smp, e->clock.drained, (int)n, e->drain_dev, e->pack_stream);
   AZ_HIP(hipGetLastError());
   AZ_HIP(hipMemcpyAsync(e->drain_host, e->drain_dev, (size_t)n * rec, hipMemcpyDeviceToHost, e->pack_stream));
   AZ_HIP(hipStreamSynchronize(e->pack_stream));
@@ -1417,7 +1237,7 @@ int az_selfplay_drain(az_engine* e, int64_t max_games, int64_t* n_out, int64_t* 
       for (size_t p = 0; p < HW; ++p) moves[i * HW + p] = mv[p];
     if (boards) memcpy(boards + i * HW * HW, mv + HW, HW * HW);
   }
-  e->drained += n;
+  e->clock.drained += n;
   *n_out = n;
   return 0;
 }
@@ -1481,11 +1301,11 @@ int az_tree_search_noise(az_engine* e, int n_sims, const double* noise, int rows
   az::TreeDev& t = e->whole.t;
   if (n > e->noise_cap) {  // grown on demand, kept for the next searches
     double* buf = nullptr;
-    if ((rc = e->alloc(&buf, n))) return rc;
+    if ((rc = e->mem.alloc(&buf, n, false))) return rc;
     e->noise_buf = buf;
     e->noise_cap = n;
   }
-  if (!t.noise_cur && (rc = e->alloc(&t.noise_cur, S))) return rc;
+  if (!t.noise_cur && (rc = e->mem.alloc(&t.noise_cur, S, false))) return rc;
   if (rows) AZ_HIP(hipMemcpyAsync(e->noise_buf, noise, S * rows * e->g.A * sizeof(double), hipMemcpyHostToDevice,
                                   e->stream));
   AZ_HIP(hipMemsetAsync(t.noise_cur, 0, S * sizeof(int32_t), e->stream));

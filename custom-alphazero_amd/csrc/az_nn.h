@@ -245,9 +245,10 @@ int conv16_prescale(const double* w, size_t n, const double* w2, size_t n2);
 // weights [3][3][cin_n][128] (+ 1x1 residual [128][128]) -> uint16 fp16 bits
 void conv16_pack(const double* w3, int cin_n, const double* wr, int e, std::vector<uint16_t>& out);
 // Folds and uploads the network weights (Keras names, model/weights.py);
-// device buffers are appended to `owned` (az_engine.hip)
+// device buffers are allocated from `owned` (az_engine.hip; az_host.h)
+struct DeviceAllocs;
 int load_network(NetDev& net, const ::az_tensor* tensors, int n, int in_ch, int HW, int A,
-                 double eps, std::vector<void*>& owned);
+                 double eps, DeviceAllocs& owned);
 // x: [n][HW][4] fp32 (in_ch == 4), or the zero-padded planes [n][HW][F] (in_ch > 4) as split16 rows
 // (AZ_CONV_F16X2) or fp32 (AZ_CONV_DIRECT); count (device int, may be null -> n_max) is the live
 // batch; boards (optional): one-hot input straight from the eval queue's boards (bitwise the same

@@ -17,11 +17,10 @@
 #include <vector>
 
 #include "../../include/az.h"
+#include "az_host.h"
 #include "az_train.h"
 
 namespace az {
-int fail_abi(int code, const std::string& msg);  // az_engine.hip (az_last_error)
-
 namespace train {
 namespace {
 
@@ -706,13 +705,6 @@ namespace {
 using az::fail_abi;
 namespace T = az::train;
 
-#define AZT_HIP(expr)                                                                        \
-  do {                                                                                       \
-    hipError_t err__ = (expr);                                                               \
-    if (err__ != hipSuccess)                                                                 \
-      return fail_abi(AZ_E_HIP, std::string(#expr) + ": " + hipGetErrorString(err__));       \
-  } while (0)
-
 struct Tensor {
   int64_t off = 0, numel = 0;
   bool trainable = true;
@@ -754,31 +746,15 @@ struct az_trainer {
   double* sq_partial = nullptr;
   float* losses = nullptr;
   uint16_t* tapmask = nullptr;
-  std::vector<void*> owned;
+  az::DeviceAllocs mem;  // every buffer starts zeroed
 };
 
 namespace {
 
-template <typename P>
-int dev_alloc(az_trainer* tr, P** p, size_t count) {
-  void* q = nullptr;
-  AZT_HIP(hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(P)));
-  AZT_HIP(hipMemset(q, 0, std::max<size_t>(count, 1) * sizeof(P)));
-  tr->owned.push_back(q);
-  *p = static_cast<P*>(q);
-  return AZ_OK;
-}
-
-#define AZT_TRY(expr)          \
-  do {                         \
-    const int rc__ = (expr);   \
-    if (rc__ != AZ_OK) return rc__; \
-  } while (0)
-
 void free_trainer(az_trainer* tr) {
   (void)hipSetDevice(tr->device);
   if (tr->stream) (void)hipStreamSynchronize(tr->stream);
-  for (void* p : tr->owned) (void)hipFree(p);
+  tr->mem.free_all();
   if (tr->stream) (void)hipStreamDestroy(tr->stream);
   delete tr;
 }
@@ -837,42 +813,42 @@ int build_trainer(az_trainer* tr) {
 
   // ---- device memory, once for max_batch
   const size_t rows = (size_t)tr->max_batch * HW, B = tr->max_batch;
-  AZT_TRY(dev_alloc(tr, &tr->w, off));
-  AZT_TRY(dev_alloc(tr, &tr->g, tr->n_train));
-  AZT_TRY(dev_alloc(tr, &tr->m, tr->n_train));
-  AZT_TRY(dev_alloc(tr, &tr->bmean, 2 * ns));
+  AZ_TRY(tr->mem.alloc(&tr->w, off, true));
+  AZ_TRY(tr->mem.alloc(&tr->g, tr->n_train, true));
+  AZ_TRY(tr->mem.alloc(&tr->m, tr->n_train, true));
+  AZ_TRY(tr->mem.alloc(&tr->bmean, 2 * ns, true));
   tr->bvar = tr->bmean + ns;
-  AZT_TRY(dev_alloc(tr, &tr->invstd, ns));
-  AZT_TRY(dev_alloc(tr, &tr->x, rows * 4));
-  AZT_TRY(dev_alloc(tr, &tr->pi, B * A));
-  AZT_TRY(dev_alloc(tr, &tr->z, B));
-  for (Unit& u : U) AZT_TRY(dev_alloc(tr, &u.y, rows * u.cout));
+  AZ_TRY(tr->mem.alloc(&tr->invstd, ns, true));
+  AZ_TRY(tr->mem.alloc(&tr->x, rows * 4, true));
+  AZ_TRY(tr->mem.alloc(&tr->pi, B * A, true));
+  AZ_TRY(tr->mem.alloc(&tr->z, B, true));
+  for (Unit& u : U) AZ_TRY(tr->mem.alloc(&u.y, rows * u.cout, true));
   tr->h.resize(depth + 1);
   tr->a1.resize(depth);
-  for (auto& p : tr->h) AZT_TRY(dev_alloc(tr, &p, rows * F));
-  for (auto& p : tr->a1) AZT_TRY(dev_alloc(tr, &p, rows * F));
-  AZT_TRY(dev_alloc(tr, &tr->hp, rows * 2));
-  AZT_TRY(dev_alloc(tr, &tr->hv, rows));
-  AZT_TRY(dev_alloc(tr, &tr->ga, rows * F));
-  AZT_TRY(dev_alloc(tr, &tr->gb, rows * F));
-  AZT_TRY(dev_alloc(tr, &tr->dy1, rows * F));
-  AZT_TRY(dev_alloc(tr, &tr->dy2, rows * F));
-  AZT_TRY(dev_alloc(tr, &tr->ghp, rows * 2));
-  AZT_TRY(dev_alloc(tr, &tr->ghv, rows));
-  AZT_TRY(dev_alloc(tr, &tr->dyp, rows * 2));
-  AZT_TRY(dev_alloc(tr, &tr->dyv, rows));
-  AZT_TRY(dev_alloc(tr, &tr->dlogit, B * A));
-  AZT_TRY(dev_alloc(tr, &tr->d1, B * hidden));
-  AZT_TRY(dev_alloc(tr, &tr->dpre1, B * hidden));
-  AZT_TRY(dev_alloc(tr, &tr->dpre2, B));
-  AZT_TRY(dev_alloc(tr, &tr->lossp, B));
-  AZT_TRY(dev_alloc(tr, &tr->lossv, B));
-  AZT_TRY(dev_alloc(tr, &tr->losses, 4));
+  for (auto& p : tr->h) AZ_TRY(tr->mem.alloc(&p, rows * F, true));
+  for (auto& p : tr->a1) AZ_TRY(tr->mem.alloc(&p, rows * F, true));
+  AZ_TRY(tr->mem.alloc(&tr->hp, rows * 2, true));
+  AZ_TRY(tr->mem.alloc(&tr->hv, rows, true));
+  AZ_TRY(tr->mem.alloc(&tr->ga, rows * F, true));
+  AZ_TRY(tr->mem.alloc(&tr->gb, rows * F, true));
+  AZ_TRY(tr->mem.alloc(&tr->dy1, rows * F, true));
+  AZ_TRY(tr->mem.alloc(&tr->dy2, rows * F, true));
+  AZ_TRY(tr->mem.alloc(&tr->ghp, rows * 2, true));
+  AZ_TRY(tr->mem.alloc(&tr->ghv, rows, true));
+  AZ_TRY(tr->mem.alloc(&tr->dyp, rows * 2, true));
+  AZ_TRY(tr->mem.alloc(&tr->dyv, rows, true));
+  AZ_TRY(tr->mem.alloc(&tr->dlogit, B * A, true));
+  AZ_TRY(tr->mem.alloc(&tr->d1, B * hidden, true));
+  AZ_TRY(tr->mem.alloc(&tr->dpre1, B * hidden, true));
+  AZ_TRY(tr->mem.alloc(&tr->dpre2, B, true));
+  AZ_TRY(tr->mem.alloc(&tr->lossp, B, true));
+  AZ_TRY(tr->mem.alloc(&tr->lossv, B, true));
+  AZ_TRY(tr->mem.alloc(&tr->losses, 4, true));
   const size_t rp = T::row_parts((int)rows), bp = T::board_parts(tr->max_batch);
   const size_t partial = std::max(std::max(bp * 9 * F * F, rp * 36 * F), std::max(rp * 4 * F, rp * 384));
-  AZT_TRY(dev_alloc(tr, &tr->partial, partial));
-  AZT_TRY(dev_alloc(tr, &tr->sq_partial, (size_t)(tr->n_l2 + 4095) / 4096));
-  AZT_TRY(dev_alloc(tr, &tr->tapmask, HW));
+  AZ_TRY(tr->mem.alloc(&tr->partial, partial, true));
+  AZ_TRY(tr->mem.alloc(&tr->sq_partial, (size_t)(tr->n_l2 + 4095) / 4096, true));
+  AZ_TRY(tr->mem.alloc(&tr->tapmask, HW, true));
   std::vector<uint16_t> mask(HW);
   for (int y = 0; y < H; ++y)
     for (int x = 0; x < W; ++x) {
@@ -883,10 +859,10 @@ int build_trainer(az_trainer* tr) {
       }
       mask[y * W + x] = (uint16_t)mk;
     }
-  AZT_HIP(hipMemcpy(tr->tapmask, mask.data(), HW * sizeof(uint16_t), hipMemcpyHostToDevice));
+  AZ_HIP(hipMemcpy(tr->tapmask, mask.data(), HW * sizeof(uint16_t), hipMemcpyHostToDevice));
   tr->geo = T::Geo{H, W, HW, A, hidden, tr->tapmask};
-  AZT_HIP(hipStreamCreateWithFlags(&tr->stream, hipStreamNonBlocking));
-  AZT_HIP(hipDeviceSynchronize());  // the allocations' memsets ran on the null stream
+  AZ_HIP(hipStreamCreateWithFlags(&tr->stream, hipStreamNonBlocking));
+  AZ_HIP(hipDeviceSynchronize());  // the allocations' memsets ran on the null stream
   return AZ_OK;
 }
 
@@ -907,11 +883,7 @@ int az_trainer_create(int device, const az_config* cfg, int max_batch, az_traine
   if (max_batch < 1 || (int64_t)max_batch * c.board_height * c.board_width * T::kF >= (1ll << 31))
     return fail_abi(AZ_E_INVALID, "az_trainer_create: max_batch must be >= 1 and max_batch*H*W*128 < 2^31");
   if (device < 0) return fail_abi(AZ_E_INVALID, "az_trainer_create: bad device ordinal");
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
-    return fail_abi(AZ_E_HIP, "no HIP device visible: libaz has no CPU fallback");
-  if (device >= count) return fail_abi(AZ_E_INVALID, "az_trainer_create: device ordinal out of range");
-  AZT_HIP(hipSetDevice(device));
+  AZ_TRY(az::open_device(device, "az_trainer_create: device ordinal out of range"));
   az_trainer* tr = new az_trainer();
   tr->device = device;
   tr->cfg = c;
@@ -948,23 +920,23 @@ int az_trainer_set_weights(az_trainer* tr, const az_tensor* tensors, int n) {
     if (seen[tensors[i].name]++)
       return fail_abi(AZ_E_INVALID, std::string("az_trainer_set_weights: duplicate tensor ") + tensors[i].name);
   }
-  AZT_HIP(hipSetDevice(tr->device));
-  AZT_HIP(hipStreamSynchronize(tr->stream));
+  AZ_HIP(hipSetDevice(tr->device));
+  AZ_HIP(hipStreamSynchronize(tr->stream));
   for (int i = 0; i < n; ++i) {
     const Tensor& t = tr->tensors[tensors[i].name];
-    AZT_HIP(hipMemcpy(tr->w + t.off, tensors[i].data, t.numel * sizeof(float),
-                      tensors[i].on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+    AZ_HIP(hipMemcpy(tr->w + t.off, tensors[i].data, t.numel * sizeof(float),
+                     tensors[i].on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
   }
-  AZT_HIP(hipDeviceSynchronize());
+  AZ_HIP(hipDeviceSynchronize());
   tr->has_weights = true;
   return AZ_OK;
 }
 
 int az_trainer_reset_momentum(az_trainer* tr) {
   if (!tr) return fail_abi(AZ_E_INVALID, "az_trainer_reset_momentum: null trainer");
-  AZT_HIP(hipSetDevice(tr->device));
-  AZT_HIP(hipMemsetAsync(tr->m, 0, tr->n_train * sizeof(float), tr->stream));
-  AZT_HIP(hipStreamSynchronize(tr->stream));
+  AZ_HIP(hipSetDevice(tr->device));
+  AZ_HIP(hipMemsetAsync(tr->m, 0, tr->n_train * sizeof(float), tr->stream));
+  AZ_HIP(hipStreamSynchronize(tr->stream));
   return AZ_OK;
 }
 
@@ -982,9 +954,9 @@ int az_trainer_read(az_trainer* tr, int what, const char* name, float* out, int6
   else
     return fail_abi(AZ_E_INVALID, "az_trainer_read: `what` must be AZ_TRAIN_WEIGHT, or GRAD / MOMENTUM of a "
                                   "trainable tensor");
-  AZT_HIP(hipSetDevice(tr->device));
-  AZT_HIP(hipStreamSynchronize(tr->stream));
-  AZT_HIP(hipMemcpy(out, src + t.off, numel * sizeof(float), hipMemcpyDeviceToHost));
+  AZ_HIP(hipSetDevice(tr->device));
+  AZ_HIP(hipStreamSynchronize(tr->stream));
+  AZ_HIP(hipMemcpy(out, src + t.off, numel * sizeof(float), hipMemcpyDeviceToHost));
   return AZ_OK;
 }
 
@@ -994,15 +966,15 @@ int az_trainer_step(az_trainer* tr, const float* x, const float* pi, const float
   // one board is a batch: every BatchNormalization takes its statistics over the n*H*W rows
   if (n < 1 || n > tr->max_batch) return fail_abi(AZ_E_INVALID, "az_trainer_step: n must be 1..max_batch");
   if (!tr->has_weights) return fail_abi(AZ_E_STATE, "az_trainer_step: no weights (az_trainer_set_weights first)");
-  AZT_HIP(hipSetDevice(tr->device));
+  AZ_HIP(hipSetDevice(tr->device));
   hipStream_t s = tr->stream;
   const T::Geo& g = tr->geo;
   const int HW = g.HW, A = g.A, hidden = g.hidden, depth = tr->depth;
   const int rows = n * HW;
   const float eps = (float)tr->cfg.bn_epsilon;
-  AZT_HIP(hipMemcpyAsync(tr->x, x, (size_t)rows * 4 * sizeof(float), hipMemcpyHostToDevice, s));
-  AZT_HIP(hipMemcpyAsync(tr->pi, pi, (size_t)n * A * sizeof(float), hipMemcpyHostToDevice, s));
-  AZT_HIP(hipMemcpyAsync(tr->z, z, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s));
+  AZ_HIP(hipMemcpyAsync(tr->x, x, (size_t)rows * 4 * sizeof(float), hipMemcpyHostToDevice, s));
+  AZ_HIP(hipMemcpyAsync(tr->pi, pi, (size_t)n * A * sizeof(float), hipMemcpyHostToDevice, s));
+  AZ_HIP(hipMemcpyAsync(tr->z, z, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s));
   float *w = tr->w, *gr = tr->g;
   auto tw = [&](const char* name) { return w + tr->tensors[name].off; };
   auto tg = [&](const char* name) { return gr + tr->tensors[name].off; };
@@ -1089,10 +1061,10 @@ int az_trainer_step(az_trainer* tr, const float* x, const float* pi, const float
   T::sgd_update(s, w, gr, tr->m, tr->n_train, tr->n_l2, (float)lr, (float)momentum, (float)l2);
   T::moving_update(s, w + tr->n_train, tr->bmean, tr->n_stats, (float)bn_momentum,
                    (float)T::moving_variance_factor(rows));
-  AZT_HIP(hipGetLastError());
+  AZ_HIP(hipGetLastError());
   float host_losses[3];
-  AZT_HIP(hipMemcpyAsync(host_losses, tr->losses, sizeof(host_losses), hipMemcpyDeviceToHost, s));
-  AZT_HIP(hipStreamSynchronize(s));
+  AZ_HIP(hipMemcpyAsync(host_losses, tr->losses, sizeof(host_losses), hipMemcpyDeviceToHost, s));
+  AZ_HIP(hipStreamSynchronize(s));
   if (losses) memcpy(losses, host_losses, sizeof(host_losses));
   return AZ_OK;
 }
