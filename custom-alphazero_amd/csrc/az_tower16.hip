@@ -935,9 +935,11 @@ __device__ __forceinline__ void tower16_tile(const TowerNet* __restrict__ net, c
       auto mid = [&]() {
         rescale();
         __syncthreads();
+        // (the blob pads wv1 to whole uint4s, and so does its staged place: HW * J need be no
+        // multiple of 4 for the late copy -- hidden 1 or 255; the X tile takes multiples only)
         if (wv1x)
           dma_to_lds<NT>(reinterpret_cast<uint4*>(wv1_xt ? reinterpret_cast<float*>(bufX) + TR * 48 : blob + T.off_wv1),
-                         T.blob + T.off_wv1, HW * J / 4, wave, lane);
+                         T.blob + T.off_wv1, (HW * J + 3) / 4, wave, lane);
       };
 #pragma unroll
       for (int mb = 0; mb < MBW; ++mb)
