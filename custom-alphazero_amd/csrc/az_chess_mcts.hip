@@ -1452,7 +1452,7 @@ int az_chess_stats(az_chess_engine* e, az_stats* st) {
   if ((rc = az::read_common_stats(st, h, e->t.stats, e->t.game_id, e->g.slots, e->cache.ctl, e->cache.gen_size,
                                   e->cache.mask)))
     return rc;
-  st->issued_flop_per_board = e->net.use_tower && e->net.tower ? e->net.issued_flop_per_board : 0.0;
+  st->issued_flop_per_board = e->net.use_tower && e->net.tower ? e->net.layout.main.issued_flop_per_board : 0.0;
   st->tower_small_max_boards = -1;  // (chess: one tile height)
   std::vector<az::ConvTimer*> timers = {&e->timer};
   for (CLane* L : e->lanes) timers.push_back(&L->timer);

@@ -402,14 +402,211 @@ int alloc_pool(az_engine* e, Lane* L, int64_t cap) {
   return 0;
 }
 
+// The network folded (BatchNorm into conv) on the host: kernels in Keras
+// layout and biases, in double.
+struct FoldedUnit {
+  std::vector<double> w, b;
+};
+struct FoldedNet {
+  FoldedUnit stem;  // [3][3][in_ch][F]
+  struct Block {
+    FoldedUnit conv1, conv2, res;  // [3][3][F][F] twice, the 1x1 projection [F][F]
+  };
+  std::vector<Block> blocks;
+  FoldedUnit pc, vc;      // head 1x1 convs: policy [F][2], value [F][1]
+  FoldedUnit pd, v1, v2;  // dense (no BatchNorm): policy [2HW][A], value [HW][hidden], [hidden][1]
+};
+
+[[maybe_unused]] int fold_network(const std::map<std::string, const az_tensor*>& m, int in_ch, int depth, int HW, int A,
+                                  int hidden, double eps, FoldedNet& f) {
+  const int F = 128;
+  const int64_t K = 2 * HW;
+  AZ_TRY(fold_unit(m, "stem", 3, in_ch, F, eps, f.stem.w, f.stem.b));
+  f.blocks.resize(depth);
+  for (int d = 0; d < depth; ++d) {
+    const std::string p = "block" + std::to_string(d);
+    FoldedNet::Block& k = f.blocks[d];
+    AZ_TRY(fold_unit(m, p + ".conv1", 3, F, F, eps, k.conv1.w, k.conv1.b));
+    AZ_TRY(fold_unit(m, p + ".conv2", 3, F, F, eps, k.conv2.w, k.conv2.b));
+    AZ_TRY(fold_unit(m, p + ".res", 1, F, F, eps, k.res.w, k.res.b));
+  }
+  AZ_TRY(fold_unit(m, "policy.conv", 1, F, 2, eps, f.pc.w, f.pc.b));
+  AZ_TRY(fold_unit(m, "value.conv", 1, F, 1, eps, f.vc.w, f.vc.b));
+  AZ_TRY(fetch(m, "policy.dense.kernel", K * A, f.pd.w));
+  AZ_TRY(fetch(m, "policy.dense.bias", A, f.pd.b));
+  AZ_TRY(fetch(m, "value.dense1.kernel", (int64_t)HW * hidden, f.v1.w));
+  AZ_TRY(fetch(m, "value.dense1.bias", hidden, f.v1.b));
+  AZ_TRY(fetch(m, "value.dense2.kernel", hidden, f.v2.w));
+  return fetch(m, "value.dense2.bias", 1, f.v2.b);
+}
+
+[[maybe_unused]] std::vector<float> to_float(const std::vector<double>& v) { return {v.begin(), v.end()}; }
+
+// a block's 3x3 conv (+ its 1x1 residual), uploaded in this order: the direct kernel's fragments of
+// [F][9F] (with the residual [F][10F]), the conv16 pack, the folded bias (+ the residual's)
+[[maybe_unused]] int upload_block_conv(az::DeviceAllocs& owned, const FoldedUnit& c, const FoldedUnit* res,
+                                       float** frag, uint16_t** pack, float* scale, float** bias) {
+  const int F = 128, K = (res ? 10 : 9) * F;
+  std::vector<float> wt((size_t)F * K), bt(F);
+  for (int n = 0; n < F; ++n) {
+    for (int k = 0; k < 9 * F; ++k) wt[(size_t)n * K + k] = (float)c.w[(size_t)k * F + n];
+    for (int ch = 0; res && ch < F; ++ch) wt[(size_t)n * K + 9 * F + ch] = (float)res->w[(size_t)ch * F + n];
+    bt[n] = (float)(res ? c.b[n] + res->b[n] : c.b[n]);
+  }
+  AZ_TRY(upload(owned, frag, pack_fragments(wt, F, K)));
+  AZ_TRY(upload_conv16(owned, pack, scale, c.w, F, res ? &res->w : nullptr));
+  return upload(owned, bias, bt);
+}
+
+// the per-layer kernels' buffers (both conv algorithms; the tower reads the conv16 packs too)
+[[maybe_unused]] int upload_layers(az::NetDev& net, const FoldedNet& f, int in_ch, int HW, int A,
+                                   az::DeviceAllocs& owned) {
+  const int F = 128;
+  AZ_TRY(upload(owned, &net.stem_b, to_float(f.stem.b)));
+  if (in_ch == 4) {  // [3][3][4][F]: Keras order == [tap*4 + c][F]
+    AZ_TRY(upload(owned, &net.stem_w, to_float(f.stem.w)));
+  } else {  // [3][3][in_ch][F]: the conv16 pack pads the channels; direct: [3][3][F][F] zero-padded
+    AZ_TRY(upload_conv16(owned, &net.stem_k, &net.stem_scale, f.stem.w, in_ch, nullptr));
+    std::vector<float> wt((size_t)F * 9 * F, 0.f);
+    for (int tap = 0; tap < 9; ++tap)
+      for (int c = 0; c < in_ch; ++c)
+        for (int o = 0; o < F; ++o)
+          wt[(size_t)o * 9 * F + tap * F + c] = (float)f.stem.w[((size_t)tap * in_ch + c) * F + o];
+    AZ_TRY(upload(owned, &net.stem_d, pack_fragments(wt, F, 9 * F)));
+  }
+  net.in_ch = in_ch;
+  const int depth = (int)f.blocks.size();
+  for (auto* v : {&net.c1_w, &net.c1_b, &net.c2_w, &net.c2_b}) v->assign(depth, nullptr);
+  for (auto* v : {&net.k1, &net.k2}) v->assign(depth, nullptr);
+  for (auto* v : {&net.k1_scale, &net.k2_scale}) v->assign(depth, 1.f);
+  for (int d = 0; d < depth; ++d) {
+    const FoldedNet::Block& k = f.blocks[d];
+    AZ_TRY(upload_block_conv(owned, k.conv1, nullptr, &net.c1_w[d], &net.k1[d], &net.k1_scale[d], &net.c1_b[d]));
+    AZ_TRY(upload_block_conv(owned, k.conv2, &k.res, &net.c2_w[d], &net.k2[d], &net.k2_scale[d], &net.c2_b[d]));
+  }
+  AZ_TRY(upload(owned, &net.pc_w, to_float(f.pc.w)));
+  AZ_TRY(upload(owned, &net.pc_b, to_float(f.pc.b)));
+  AZ_TRY(upload(owned, &net.vc_w, to_float(f.vc.w)));
+  AZ_TRY(upload(owned, &net.vc_b, to_float(f.vc.b)));
+  const std::vector<float> pdw = to_float(f.pd.w);
+  AZ_TRY(upload(owned, &net.pd_w, pdw));
+  AZ_TRY(upload(owned, &net.pd_b, to_float(f.pd.b)));
+  if (A > az::kMaxActions) {
+    const int K = 2 * HW, tiles = (A + 63) / 64;
+    std::vector<float> t((size_t)tiles * K * 64, 0.f);
+    for (int k = 0; k < K; ++k)
+      for (int o = 0; o < A; ++o) t[((size_t)(o / 64) * K + k) * 64 + (o % 64)] = pdw[(size_t)k * A + o];
+    AZ_TRY(upload(owned, &net.pd_wt, t));
+  }
+  AZ_TRY(upload(owned, &net.v1_w, to_float(f.v1.w)));
+  AZ_TRY(upload(owned, &net.v1_b, to_float(f.v1.b)));
+  AZ_TRY(upload(owned, &net.v2_w, to_float(f.v2.w)));
+  return upload(owned, &net.v2_b, to_float(f.v2.b));
+}
+
+// the tower's small-weight blob (TowerNet::blob) in the order and at the offsets tower16_blob_offsets states
+[[maybe_unused]] int tower_blob(const FoldedNet& f, const az::TowerBlob& at, std::vector<float>& blob) {
+  bool drift = false;
+  auto put = [&](int off, const std::vector<float>& v) {
+    drift = drift || off != (int)blob.size();
+    blob.insert(blob.end(), v.begin(), v.end());
+    while (blob.size() % 4) blob.push_back(0.f);
+  };
+  std::vector<float> b1, b2;
+  for (const FoldedNet::Block& k : f.blocks)
+    for (size_t i = 0; i < k.conv1.b.size(); ++i) {
+      b1.push_back((float)k.conv1.b[i]);
+      b2.push_back((float)(k.conv2.b[i] + k.res.b[i]));
+    }
+  put(at.off_b1, b1);
+  put(at.off_b2, b2);
+  put(at.off_stemb, to_float(f.stem.b));
+  put(at.off_wpc, to_float(f.pc.w));
+  put(at.off_wvc, to_float(f.vc.w));
+  put(at.off_hb, {(float)f.pc.b[0], (float)f.pc.b[1], (float)f.vc.b[0], (float)f.v2.b[0]});
+  put(at.off_bpd, to_float(f.pd.b));
+  put(at.off_bv1, to_float(f.v1.b));
+  put(at.off_wv2, to_float(f.v2.w));
+  put(at.off_wpd, to_float(f.pd.w));
+  put(at.off_wv1, to_float(f.v1.w));
+  if (drift || (int)blob.size() != at.floats)
+    return fail(AZ_E_STATE, "internal: the tower's blob and tower16_blob_offsets disagree");
+  return 0;
+}
+
+// The one place that writes TowerNet's layout fields: the layout, the blob
+// and the slot plans uploaded, the device view filled from them.
+[[maybe_unused]] int upload_tower(az::NetDev& net, const az::TowerLayout& L, const FoldedNet& f, bool rows_stem,
+                                  az::DeviceAllocs& owned) {
+  az::TowerNet tn{};
+  tn.stem_s = 1.f;
+  if (!rows_stem) {  // the 4-plane stem as a pack of its own; the input-row form reads the conv16 pack stem_k
+    const int e = az::conv16_prescale(f.stem.w.data(), f.stem.w.size(), nullptr, 0);
+    std::vector<uint16_t> pack;
+    az::tower16_stem_pack(f.stem.w.data(), e, pack);
+    uint16_t* stem16 = nullptr;
+    AZ_TRY(upload_new(owned, &stem16, pack));
+    tn.stem16 = reinterpret_cast<const uint4*>(stem16);
+    tn.stem_s = std::ldexp(1.f, e - 12);
+  }
+  for (int d = 0; d < net.depth; ++d) {
+    tn.k1[d] = reinterpret_cast<const uint4*>(net.k1[d]);
+    tn.k2[d] = reinterpret_cast<const uint4*>(net.k2[d]);
+    tn.s1[d] = net.k1_scale[d];
+    tn.s2[d] = net.k2_scale[d];
+  }
+  tn.stem_k = rows_stem ? reinterpret_cast<const uint4*>(net.stem_k) : nullptr;
+  tn.stem_ks = net.stem_scale;
+  const az::TowerBlob& b = L.blob;
+  tn.blob_floats = b.floats;
+  tn.off_b1 = b.off_b1;
+  tn.off_b2 = b.off_b2;
+  tn.off_stemb = b.off_stemb;
+  tn.off_wpc = b.off_wpc;
+  tn.off_wvc = b.off_wvc;
+  tn.off_hb = b.off_hb;
+  tn.off_bpd = b.off_bpd;
+  tn.off_bv1 = b.off_bv1;
+  tn.off_wv2 = b.off_wv2;
+  tn.off_wpd = b.off_wpd;
+  tn.off_wv1 = b.off_wv1;
+  tn.wv1_xtile = L.wv1_xtile;
+  tn.dbuf = L.dbuf;
+  tn.depth = net.depth;
+  tn.hidden = net.hidden;
+  // one tile height's fields (a null slot_pix: natural order)
+  auto tiles = [&](const az::TowerTiles& t, int& rows, int& staged, int& wpd, int& wv1, const int** pix, int skip[2]) {
+    rows = t.rows;
+    staged = t.staged_floats;
+    wpd = t.wpd_lds;
+    wv1 = t.wv1_lds;
+    skip[0] = t.skip[0];
+    skip[1] = t.skip[1];
+    return t.slot_pix.empty() ? 0 : upload_new(owned, const_cast<int**>(pix), t.slot_pix);
+  };
+  AZ_TRY(tiles(L.main, tn.tile_rows, tn.staged_floats, tn.wpd_lds, tn.wv1_lds, &tn.slot_pix, tn.skip));
+  AZ_TRY(tiles(L.alt, tn.alt_rows, tn.alt_staged_floats, tn.alt_wpd_lds, tn.alt_wv1_lds, &tn.alt_slot_pix,
+               tn.alt_skip));
+  tn.alt_max_boards = L.alt_max_boards;
+  if (!net.tower) AZ_TRY(owned.alloc(&net.tower, 1, false));
+  std::vector<float> blob;
+  float* qb = nullptr;
+  AZ_TRY(tower_blob(f, L.blob, blob));
+  AZ_TRY(upload_new(owned, &qb, blob));
+  tn.blob = qb;
+  AZ_HIP(hipMemcpy(net.tower, &tn, sizeof(az::TowerNet), hipMemcpyHostToDevice));
+  return 0;
+}
+
 }  // namespace
 
 namespace az {
-// Folds (BatchNorm into conv) and uploads the network weights, Keras names
-// of custom_alphazero/model/weights.py.  in_ch = 4: the Connect-N stem
-// kernels (stem_w [36][F]; the one-launch tower's stem16 pack and its
-// small-weight blob); in_ch > 4 (chess, 118 planes): the stem is one more
-// conv16 3x3 conv over the input zero-padded to F channels (stem_k).
+// Folds and uploads the network weights, Keras names of
+// custom_alphazero/model/weights.py.  in_ch = 4: the Connect-N stem kernels
+// (stem_w [36][F]; the one-launch tower's stem16 pack and its small-weight
+// blob); in_ch > 4 (chess, 118 planes): the stem is one more conv16 3x3 conv
+// over the input zero-padded to F channels (stem_k), which is also the stem
+// of the tower's input-row form.
 int load_network(NetDev& net, const az_tensor* tensors, int n, int in_ch, int HW, int A, double eps,
                  DeviceAllocs& owned) {
   std::map<std::string, const az_tensor*> m;
@@ -417,260 +614,23 @@ int load_network(NetDev& net, const az_tensor* tensors, int n, int in_ch, int HW
     if (!tensors[i].name || !tensors[i].data) return fail(AZ_E_INVALID, "tensor without name/data");
     m[tensors[i].name] = &tensors[i];
   }
-  const int F = 128, hidden = net.hidden;
-  if (in_ch < 1 || in_ch > F) return fail(AZ_E_INVALID, "input planes must be 1..128");
-  std::vector<double> w, b, wr, br;
-  int rc;
-  if ((rc = fold_unit(m, "stem", 3, in_ch, F, eps, w, b))) return rc;
-  // host copies for the one-launch tower (tower16_kernel): its stem pack and the small-weight blob
-  // (in_ch > 4, chess: the input-row form, whose stem is the conv16 pack stem_k)
-  const bool tower = net.use_tower && (in_ch == 4 || HW == 64);
-  const bool rows_tower = tower && in_ch > 4;
-  std::vector<float> tb_b1, tb_b2, tb_stemb(b.begin(), b.end()), tb_pcw, tb_vcw, tb_hb(4, 0.f), tb_pdw, tb_pdb,
-      tb_v1w, tb_v1b, tb_v2w;
-  uint16_t* stem16 = nullptr;
-  float stem_s = 1.f;
-  if (tower && !rows_tower) {
-    const int e = conv16_prescale(w.data(), w.size(), nullptr, 0);
-    std::vector<uint16_t> pack;
-    tower16_stem_pack(w.data(), e, pack);
-    stem_s = std::ldexp(1.f, e - 12);
-    if ((rc = upload_new(owned, &stem16, pack))) return rc;
-  }
-  {
-    std::vector<float> bs(F);
-    for (int i = 0; i < F; ++i) bs[i] = (float)b[i];
-    if ((rc = upload(owned, &net.stem_b, bs))) return rc;
-    if (in_ch == 4) {  // [3][3][4][F] -> [tap*4 + c][F]
-      std::vector<float> ws(36 * F);
-      for (int i = 0; i < 36 * F; ++i) ws[i] = (float)w[i];  // Keras order == (tap, c, n)
-      if ((rc = upload(owned, &net.stem_w, ws))) return rc;
-    } else {  // [3][3][in_ch][F]: the conv16 pack pads the channels; direct: [3][3][F][F] zero-padded
-      if ((rc = upload_conv16(owned, &net.stem_k, &net.stem_scale, w, in_ch, nullptr))) return rc;
-      std::vector<float> wt((size_t)F * 9 * F, 0.f);
-      for (int tap = 0; tap < 9; ++tap)
-        for (int c = 0; c < in_ch; ++c)
-          for (int o = 0; o < F; ++o) wt[(size_t)o * 9 * F + tap * F + c] = (float)w[((size_t)tap * in_ch + c) * F + o];
-      if ((rc = upload(owned, &net.stem_d, pack_fragments(wt, F, 9 * F)))) return rc;
-    }
-    net.in_ch = in_ch;
-  }
-  net.c1_w.assign(net.depth, nullptr);
-  net.c1_b.assign(net.depth, nullptr);
-  net.c2_w.assign(net.depth, nullptr);
-  net.c2_b.assign(net.depth, nullptr);
-  net.k1.assign(net.depth, nullptr);
-  net.k2.assign(net.depth, nullptr);
-  net.k1_scale.assign(net.depth, 1.f);
-  net.k2_scale.assign(net.depth, 1.f);
-  for (int d = 0; d < net.depth; ++d) {
-    const std::string p = "block" + std::to_string(d);
-    if ((rc = fold_unit(m, p + ".conv1", 3, F, F, eps, w, b))) return rc;
-    std::vector<float> wt((size_t)F * 9 * F), bt(F);
-    for (int n2 = 0; n2 < F; ++n2)
-      for (int k = 0; k < 9 * F; ++k) wt[(size_t)n2 * 9 * F + k] = (float)w[(size_t)k * F + n2];
-    for (int i = 0; i < F; ++i) bt[i] = (float)b[i];
-    tb_b1.insert(tb_b1.end(), bt.begin(), bt.end());
-    if ((rc = upload(owned, &net.c1_w[d], pack_fragments(wt, F, 9 * F))) ||
-        (rc = upload_conv16(owned, &net.k1[d], &net.k1_scale[d], w, F, nullptr)) ||
-        (rc = upload(owned, &net.c1_b[d], bt)))
-      return rc;
-    if ((rc = fold_unit(m, p + ".conv2", 3, F, F, eps, w, b))) return rc;
-    if ((rc = fold_unit(m, p + ".res", 1, F, F, eps, wr, br))) return rc;
-    std::vector<float> wt2((size_t)F * 10 * F), bt2(F);
-    for (int n2 = 0; n2 < F; ++n2) {
-      for (int k = 0; k < 9 * F; ++k) wt2[(size_t)n2 * 10 * F + k] = (float)w[(size_t)k * F + n2];
-      for (int c = 0; c < F; ++c) wt2[(size_t)n2 * 10 * F + 9 * F + c] = (float)wr[(size_t)c * F + n2];
-    }
-    for (int i = 0; i < F; ++i) bt2[i] = (float)(b[i] + br[i]);
-    tb_b2.insert(tb_b2.end(), bt2.begin(), bt2.end());
-    if ((rc = upload(owned, &net.c2_w[d], pack_fragments(wt2, F, 10 * F))) ||
-        (rc = upload_conv16(owned, &net.k2[d], &net.k2_scale[d], w, F, &wr)) ||
-        (rc = upload(owned, &net.c2_b[d], bt2)))
-      return rc;
-  }
-  // heads
-  if ((rc = fold_unit(m, "policy.conv", 1, F, 2, eps, w, b))) return rc;
-  {
-    std::vector<float> a(w.begin(), w.end()), c(b.begin(), b.end());
-    tb_pcw = a;
-    tb_hb[0] = c[0];
-    tb_hb[1] = c[1];
-    if ((rc = upload(owned, &net.pc_w, a)) || (rc = upload(owned, &net.pc_b, c))) return rc;
-  }
-  if ((rc = fold_unit(m, "value.conv", 1, F, 1, eps, w, b))) return rc;
-  {
-    std::vector<float> a(w.begin(), w.end()), c(b.begin(), b.end());
-    tb_vcw = a;
-    tb_hb[2] = c[0];
-    if ((rc = upload(owned, &net.vc_w, a)) || (rc = upload(owned, &net.vc_b, c))) return rc;
-  }
-  struct DenseSpec {
-    const char* name;
-    int in, out;
-    float** w;
-    float** b;
-  } dense[] = {{"policy.dense", 2 * HW, A, &net.pd_w, &net.pd_b},
-               {"value.dense1", HW, hidden, &net.v1_w, &net.v1_b},
-               {"value.dense2", hidden, 1, &net.v2_w, &net.v2_b}};
-  for (auto& ds : dense) {
-    if ((rc = fetch(m, std::string(ds.name) + ".kernel", (int64_t)ds.in * ds.out, w))) return rc;
-    if ((rc = fetch(m, std::string(ds.name) + ".bias", ds.out, b))) return rc;
-    std::vector<float> a(w.begin(), w.end()), c(b.begin(), b.end());
-    if ((rc = upload(owned, ds.w, a)) || (rc = upload(owned, ds.b, c))) return rc;
-    if (ds.w == &net.pd_w) {
-      tb_pdw = a;
-      tb_pdb = c;
-    } else if (ds.w == &net.v1_w) {
-      tb_v1w = a;
-      tb_v1b = c;
-    } else {
-      tb_v2w = a;
-      tb_hb[3] = c[0];
-    }
-    if (ds.w == &net.pd_w && A > kMaxActions) {
-      const int K = ds.in, tiles = (A + 63) / 64;
-      std::vector<float> t((size_t)tiles * K * 64, 0.f);
-      for (int k = 0; k < K; ++k)
-        for (int o = 0; o < A; ++o) t[((size_t)(o / 64) * K + k) * 64 + (o % 64)] = a[(size_t)k * A + o];
-      if ((rc = upload(owned, &net.pd_wt, t))) return rc;
-    }
-  }
-  if (tower) {
-    TowerNet tn{};
-    for (int d = 0; d < net.depth; ++d) {
-      tn.k1[d] = reinterpret_cast<const uint4*>(net.k1[d]);
-      tn.k2[d] = reinterpret_cast<const uint4*>(net.k2[d]);
-      tn.s1[d] = net.k1_scale[d];
-      tn.s2[d] = net.k2_scale[d];
-    }
-    tn.stem16 = reinterpret_cast<const uint4*>(stem16);
-    tn.stem_s = stem_s;
-    tn.stem_k = rows_tower ? reinterpret_cast<const uint4*>(net.stem_k) : nullptr;
-    tn.stem_ks = net.stem_scale;
-    // the small-weight blob (TowerNet), every part padded to a multiple of 4 floats
-    std::vector<float> blob;
-    auto put = [&](const std::vector<float>& v) {
-      const int off = (int)blob.size();
-      blob.insert(blob.end(), v.begin(), v.end());
-      while (blob.size() % 4) blob.push_back(0.f);
-      return off;
-    };
-    tn.off_b1 = put(tb_b1);
-    tn.off_b2 = put(tb_b2);
-    tn.off_stemb = put(tb_stemb);
-    tn.off_wpc = put(tb_pcw);
-    tn.off_wvc = put(tb_vcw);
-    tn.off_hb = put(tb_hb);
-    tn.off_bpd = put(tb_pdb);
-    tn.off_bv1 = put(tb_v1b);
-    tn.off_wv2 = put(tb_v2w);
-    tn.off_wpd = put(tb_pdw);
-    tn.off_wv1 = put(tb_v1w);
-    tn.blob_floats = (int)blob.size();
-    // the layout: 128/96-row tiles double-buffered, else one tile in place;
-    // per layout the largest staging that fits: the whole blob, then without
-    // wv1, then without wpd too (those then read from L2)
-    // (the input-row form runs no dense head: the biases and 1x1 head weights only)
-    const int prefix[3] = {rows_tower ? tn.off_bpd : tn.blob_floats, tn.off_wv1, tn.off_wpd};
-    struct Layout {
-      int tr;
-      bool db;
-    } layouts[2] = {{tower16_tile_rows(HW), true}, {tower16_tile_rows(HW), false}};
-    bool found = false;
-    for (int li = 0; li < 2 && !found; ++li) {
-      const Layout L = layouts[li];
-      if (!L.tr || (!rows_tower && !tower16_heads_fit(HW, L.tr, A, net.hidden, L.db))) continue;
-      if (rows_tower && (L.tr != 128 || tower16_lds_bytes(HW, L.tr, prefix[0], L.db) > kTowerLdsMax)) continue;
-      for (int i = 0; i < (rows_tower ? 1 : 3) && !found; ++i)
-        if (tower16_lds_bytes(HW, L.tr, prefix[i], L.db) <= kTowerLdsMax) {
-          tn.tile_rows = L.tr;
-          tn.dbuf = L.db;
-          tn.staged_floats = prefix[i];
-          tn.wv1_lds = i == 0 && !rows_tower;
-          tn.wpd_lds = i <= 1 && !rows_tower;
-          found = true;
-        }
-    }
-    if (!found) {  // the per-layer kernels instead (same arithmetic)
+  if (in_ch < 1 || in_ch > 128) return fail(AZ_E_INVALID, "input planes must be 1..128");
+  FoldedNet f;
+  AZ_TRY(fold_network(m, in_ch, net.depth, HW, A, net.hidden, eps, f));
+  AZ_TRY(upload_layers(net, f, in_ch, HW, A, owned));
+  if (net.use_tower && (in_ch == 4 || HW == 64)) {
+    int dev = 0, cus = 0;
+    AZ_HIP(hipGetDevice(&dev));
+    AZ_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    const bool rows_stem = in_ch > 4;
+    net.layout = tower16_choose_layout({net.board_h, net.board_w, A, net.depth, net.hidden, rows_stem,
+                                        net.tower_natural_order, net.lanes, cus});
+    if (net.layout.ok) {
+      AZ_TRY(upload_tower(net, net.layout, f, rows_stem, owned));
+    } else {  // the per-layer kernels instead (same arithmetic)
       net.use_tower = false;
       if (net.board_w > 16) net.algo = AZ_CONV_DIRECT;
-      net.ready = true;
-      return 0;
     }
-    tn.wv1_xtile = !rows_tower && tn.dbuf && !tn.wv1_lds && tower16_wv1_xtile_fits(HW, tn.tile_rows, net.hidden);
-    // the slot plan: border blocks skip the taps past their edge
-    // (az_config.tower_natural_order: natural order, no skips -- bitwise the same outputs)
-    {
-      std::vector<int> pix;
-      int skip[2] = {0, 0};
-      if (!net.tower_natural_order && net.board_h * net.board_w == HW)
-        tower16_slot_plan(net.board_h, net.board_w, tn.tile_rows, pix, skip);
-      tn.slot_pix = nullptr;
-      tn.skip[0] = skip[0];
-      tn.skip[1] = skip[1];
-      if (!pix.empty()) {
-        int* q = nullptr;
-        if ((rc = upload_new(owned, &q, pix))) return rc;
-        tn.slot_pix = q;
-      }
-    }
-    // dual launches (tower16_dual_kernel): boards of 33-48 cells (Connect-4)
-    // in 128-row tiles of three may also run 96-row tiles of two, with a
-    // slot plan of their own, when a launch holds at most two boards per CU
-    // that the lanes' towers leave each other (2 * CUs / lanes: Connect-4 at
-    // configs[1], ~120 live boards per lane launch with the LRU cache, gains
-    // 4.4%; at 373 or 1113 boards the 96-row tiles lose 20%, profiles/r6/)
-    tn.alt_rows = 0;
-    tn.alt_slot_pix = nullptr;
-    tn.alt_skip[0] = tn.alt_skip[1] = 0;
-    tn.alt_max_boards = -1;
-    tn.alt_staged_floats = tn.alt_wpd_lds = tn.alt_wv1_lds = 0;
-    if (!rows_tower && tn.tile_rows == 128 && tn.dbuf && tower16_boards_per_tile(HW, 128) == 3 &&
-        tower16_boards_per_tile(HW, 96) == 2 && tower16_heads_fit(HW, 96, A, net.hidden, true)) {
-      int dev = 0, cus = 0;
-      AZ_HIP(hipGetDevice(&dev));
-      AZ_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-      tn.alt_rows = 96;
-      tn.alt_max_boards = 2 * std::max(1, cus / std::max(1, net.lanes));
-      // the largest staging the 96-row layout holds (it has 64 rows fewer
-      // than the 128-row one: the whole blob, where 128 rows leave wv1 in L2)
-      for (int i = 0; i < 3; ++i)
-        if (tower16_lds_bytes(HW, 96, prefix[i], true) <= kTowerLdsMax) {
-          tn.alt_staged_floats = prefix[i];
-          tn.alt_wv1_lds = i == 0;
-          tn.alt_wpd_lds = i <= 1;
-          break;
-        }
-      std::vector<int> pix;
-      int skip[2] = {0, 0};
-      if (!net.tower_natural_order && net.board_h * net.board_w == HW)
-        tower16_slot_plan(net.board_h, net.board_w, 96, pix, skip);
-      tn.alt_skip[0] = skip[0];
-      tn.alt_skip[1] = skip[1];
-      if (!pix.empty()) {
-        int* q = nullptr;
-        if ((rc = upload_new(owned, &q, pix))) return rc;
-        tn.alt_slot_pix = q;
-      }
-    }
-    tn.depth = net.depth;
-    tn.hidden = net.hidden;
-    if (!net.tower && (rc = owned.alloc(&net.tower, 1, false))) return rc;
-    float* qb = nullptr;
-    if ((rc = upload_new(owned, &qb, blob))) return rc;
-    tn.blob = qb;
-    AZ_HIP(hipMemcpy(net.tower, &tn, sizeof(TowerNet), hipMemcpyHostToDevice));
-    net.tower_staged = tn.staged_floats;
-    net.tower_dbuf = tn.dbuf != 0;
-    net.tower_rows = tn.tile_rows;
-    net.tower_alt_rows = tn.alt_rows;
-    net.tower_alt_staged = tn.alt_staged_floats;
-    // (chess: as self-play runs it, the stem's known-zero input chunks 0-1 skipped)
-    net.issued_flop_per_board = tower16_issued_flop_per_board(HW, tn.tile_rows, net.depth, tn.skip, rows_tower, 2);
-    net.issued_flop_per_board_small =
-        tn.alt_rows ? tower16_issued_flop_per_board(HW, tn.alt_rows, net.depth, tn.alt_skip, rows_tower, 2) : 0.0;
-    net.tower_small_max_boards = tn.alt_rows ? tn.alt_max_boards : -1;
   }
   net.ready = true;
   return 0;
@@ -862,7 +822,7 @@ int az_engine_create(int device, const az_config* cfg, az_engine** out) {
   e->net.board_w = g.W;
   e->net.algo = c.conv_algo == AZ_CONV_F16X2_LAYERS ? AZ_CONV_F16X2 : c.conv_algo;
   // AZ_CONV_F16X2: the one-launch tower when the network fits it (1 <= depth
-  // <= 16, value_hidden <= 256, the head weights in LDS: load_network),
+  // <= 16, value_hidden <= 256, a layout from tower16_choose_layout: load_network),
   // otherwise quietly the same arithmetic per layer -- or, where the per-layer
   // kernels do not apply (depth 0: the heads are fused into the last conv2;
   // boards wider than 16), the fp32 MFMA path; every form within NET_TOL
@@ -1042,9 +1002,10 @@ int az_stats_get(az_engine* e, az_stats* st) {
     for (Lane* L : e->lanes) st->arena_pool_edges += 2 * L->pool_cap;
     st->arena_pool_high = (int64_t)h[az::kStatPoolHigh];
   }
-  st->issued_flop_per_board = e->net.issued_flop_per_board;
-  st->issued_flop_per_board_small = e->net.issued_flop_per_board_small;
-  st->tower_small_max_boards = e->net.tower_small_max_boards;
+  const az::TowerLayout& tl = e->net.layout;  // (all zero, no alt tiles, where the tower is not used)
+  st->issued_flop_per_board = tl.main.issued_flop_per_board;
+  st->issued_flop_per_board_small = tl.alt.issued_flop_per_board;
+  st->tower_small_max_boards = tl.alt_max_boards;
   return 0;
 }
 

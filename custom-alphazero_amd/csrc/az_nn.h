@@ -1,17 +1,17 @@
 // az_nn.h -- device-side network weights and the forward launchers.
 #pragma once
+#include <cstddef>
 #include <vector>
 
 #include "../../include/az.h"
 #include "az_device.h"
+#include "az_tower_layout.h"
 
 namespace az {
 
 // tower16_kernel (az_tower16.hip): the whole Connect-N forward in one launch.
 // Its view of the network, resident in device memory (kernel reads it with
 // scalar loads).
-constexpr int kTowerMaxDepth = 16;   // residual blocks
-constexpr int kTowerMaxBoards = 8;   // boards per workgroup tile
 struct TowerNet {
   const uint4* k1[kTowerMaxDepth];   // conv16 packs: conv1 (36 k-steps)
   const uint4* k2[kTowerMaxDepth];   // conv2 + 1x1 projection residual (40)
@@ -35,7 +35,7 @@ struct TowerNet {
   int wv1_xtile;                     // not staged, but DMA'd behind the heads' partials in X's tile (dbuf)
   int dbuf;                          // two activation tiles (else one, updated in place)
   int depth, hidden;
-  int tile_rows;                     // 96, 128 or 256 pixel rows per workgroup tile
+  int tile_rows;                     // 96, 128 or 192 pixel rows per workgroup tile
   // slot plan (tower16_slot_plan; null: natural order, no skips): the pixel
   // word of each of a full tile's slots, and per M half the blocks each tap
   // skips (2 bits per tap over the wave's blocks 0 and 1)
@@ -52,37 +52,18 @@ struct TowerNet {
   // value dense wv1 included, where the 128-row one leaves wv1 in L2)
   int alt_staged_floats, alt_wpd_lds, alt_wv1_lds;
 };
-// the slot plan of 128-row tiles: border blocks (16 slots whose pixels all
-// sit on one board edge) skip the three taps that read past that edge; empty
-// vectors when no plan applies (then natural order)
-void tower16_slot_plan(int H, int W, int tile_rows, std::vector<int>& slot_pix, int skip[2]);
-// MFMA FLOP tower16_kernel issues per board: a full tile's stem + 2 depth
-// convs (+ the 1x1 projection k-steps) less the plan's skipped taps, / boards
-// (rows_stem: the input-row stem, stem_chunks of its 4 input chunks computed)
-double tower16_issued_flop_per_board(int HW, int tile_rows, int depth, const int skip[2], bool rows_stem = false,
-                                     int stem_chunks = 4);
-// 0 when the board does not fit a tile (HW > 128); else 96 or 128 (big:
-// 256-row tiles, 16 M blocks, each wave 128 rows x 32 channels -- half the
-// weight stream per FLOP; single tile in place, the LDS holds no second)
-int tower16_tile_rows(int HW);
-int tower16_boards_per_tile(int HW, int tile_rows);
-// LDS of one workgroup: activation rows (one or two tiles + zero rows) +
-// bookkeeping + staged blob floats
-size_t tower16_lds_bytes(int HW, int tile_rows, int staged_floats, bool dbuf);
-// whether the heads' scratch (features, logits, partials) fits the tiles
-bool tower16_heads_fit(int HW, int tile_rows, int A, int hidden, bool dbuf);
-// whether wv1 [HW][hidden] fits X's tile behind the heads' partials (dbuf)
-bool tower16_wv1_xtile_fits(int HW, int tile_rows, int hidden);
-constexpr size_t kTowerLdsMax = 160 * 1024;
+// the kernels read TowerNet with scalar loads at fixed offsets
+static_assert(sizeof(TowerNet) == 560 && offsetof(TowerNet, blob) == 416 && offsetof(TowerNet, tile_rows) == 500 &&
+                  offsetof(TowerNet, slot_pix) == 504 && offsetof(TowerNet, alt_wv1_lds) == 556,
+              "TowerNet is the device's view: do not reorder, add or remove members");
 // host: folded stem [3][3][4][F] (Keras order) -> the stem16 pack with prescale e
 void tower16_stem_pack(const double* w, int e, std::vector<uint16_t>& out);
 // boards (self-play: the eval queue's boards) or x ([n][HW][4] one-hot planes,
-// az_forward) -> probs [n][A], values [n]; count (device, may be null -> n_max)
-// alt_rows: the TowerNet's alternative tile height (a dual launch), 0 = none
-void launch_tower16(const TowerNet* net, int tile_rows, int alt_rows, int alt_staged_floats, int staged_floats,
-                    bool dbuf, const Board* boards,
-                    const float4* x, const int* count, int n_max, int H, int W, int A, float* probs, float* values,
-                    unsigned long long* err, hipStream_t s);
+// az_forward) -> probs [n][A], values [n]; count (device, may be null -> n_max).
+// L: the layout the TowerNet was filled from (load_network); with alt tiles a dual launch
+void launch_tower16(const TowerNet* net, const TowerLayout& L, const Board* boards, const float4* x, const int* count,
+                    int n_max, int H, int W, int A, float* probs, float* values, unsigned long long* err,
+                    hipStream_t s);
 // the input-row form (chess): rows [n][HW] of 512 B split16 (t0 of F
 // channels, t1 x 2^12; az_nn's store_act4) -> the stem, the residual tower
 // and the heads' 1x1 convs; per pixel float4 (relu(p0), relu(p1), relu(v), 0)
@@ -100,9 +81,9 @@ struct TowerLeaves {
   const int32_t* path_len = nullptr;
   const int32_t* initial = nullptr;
 };
-void launch_tower16_rows(const TowerNet* net, int tile_rows, int staged_floats, bool dbuf, const void* rows,
-                         int first_chunk, const int* count, int n_max, int H, int W, float4* feat,
-                         unsigned long long* err, hipStream_t s, const TowerLeaves* leaves = nullptr);
+void launch_tower16_rows(const TowerNet* net, const TowerLayout& L, const void* rows, int first_chunk,
+                         const int* count, int n_max, int H, int W, float4* feat, unsigned long long* err,
+                         hipStream_t s, const TowerLeaves* leaves = nullptr);
 
 // Folded (BatchNorm-in) weights resident in HBM, packed for the kernels (not
 // Keras layouts).  AZ_CONV_F16X2 (default): conv16_kernel packs (fp16 term
@@ -114,17 +95,10 @@ struct NetDev {
   bool use_tower = false;   // Connect-N, AZ_CONV_F16X2: the whole forward in tower16_kernel (else per layer)
   bool tower_natural_order = false;  // az_config.tower_natural_order: no slot plan (A/B, bitwise the same)
   TowerNet* tower = nullptr;  // device copy of the tower's view (load_network)
-  int tower_staged = 0;       // its blob floats staged in LDS
-  bool tower_dbuf = false;    // its activations double-buffered (TowerNet::dbuf)
-  int tower_rows = 0;         // its tile rows (TowerNet::tile_rows)
-  int tower_alt_staged = 0;   // its staged blob floats (TowerNet::alt_staged_floats)
-  int tower_alt_rows = 0;     // the dual launch's alternative tile rows (TowerNet::alt_rows; 0 none)
+  TowerLayout layout;         // what it was filled from: tile heights, staging, issued FLOP (az_stats)
   int lanes = 1;              // the engine's lanes (streams whose towers share the CUs): the dual threshold
   int in_ch = 4;            // input planes: 4 (Connect-N) or 118 (chess, padded to F)
   int board_h = 0, board_w = 0;  // Connect-N board (the tower's slot plan)
-  double issued_flop_per_board_small = 0;  // the dual launch's alternative tiles (az_stats)
-  int tower_small_max_boards = -1;          // TowerNet::alt_max_boards (az_stats)
-  double issued_flop_per_board = 0;  // MFMA FLOP a forward issues per board (tower; az_stats)
   float* stem_w = nullptr;  // in_ch == 4: [36][F] (k = tap*4 + c), VALU stem kernels
   float* stem_b = nullptr;  // [F]
   // in_ch > 4 (chess): the stem is one more 3x3 conv over the zero-padded planes

@@ -709,8 +709,8 @@ void launch_forward(const NetDev& net, const void* x, const int* count, int n_ma
   const bool f16 = net.algo == AZ_CONV_F16X2;
   if (f16 && net.use_tower && net.in_ch == 4 && net.tower) {  // the whole forward in one launch
     if (timer) timer->begin(s);
-    launch_tower16(net.tower, net.tower_rows, net.tower_alt_rows, net.tower_alt_staged, net.tower_staged, net.tower_dbuf, boards,
-                   boards ? nullptr : static_cast<const float4*>(x), count, n_max, H, W, A, probs, values, net.err, s);
+    launch_tower16(net.tower, net.layout, boards, boards ? nullptr : static_cast<const float4*>(x), count, n_max, H, W,
+                   A, probs, values, net.err, s);
     if (timer) timer->end(s, 1);
     return;
   }
@@ -718,8 +718,8 @@ void launch_forward(const NetDev& net, const void* x, const int* count, int n_ma
     // chess: the stem, the tower and the heads' 1x1 convs in one launch
     // (features into act_a), then the dense heads as below
     if (timer) timer->begin(s);
-    launch_tower16_rows(net.tower, net.tower_rows, net.tower_staged, net.tower_dbuf, x, stem_first_chunk, count,
-                        n_max, H, W, static_cast<float4*>(act_a), net.err, s, leaves);
+    launch_tower16_rows(net.tower, net.layout, x, stem_first_chunk, count, n_max, H, W, static_cast<float4*>(act_a),
+                        net.err, s, leaves);
     if (timer) timer->end(s, 1);
     HeadWeights hw{net.pc_w, net.pc_b, net.vc_w, net.vc_b, net.pd_w,
                    net.pd_b, net.v1_w, net.v1_b, net.v2_w, net.v2_b};

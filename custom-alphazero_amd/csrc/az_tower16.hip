@@ -1460,6 +1460,78 @@ double tower16_issued_flop_per_board(int HW, int tr, int depth, const int skip[2
   return steps * 6 * mfma / bpw;  // 2 N blocks x 3 products per block-k-step
 }
 
+TowerBlob tower16_blob_offsets(int depth, int HW, int A, int hidden) {
+  const int F = 128;
+  TowerBlob b;
+  auto part = [&](int n) {
+    const int off = b.floats;
+    b.floats += (n + 3) & ~3;
+    return off;
+  };
+  b.off_b1 = part(depth * F);
+  b.off_b2 = part(depth * F);
+  b.off_stemb = part(F);
+  b.off_wpc = part(2 * F);
+  b.off_wvc = part(F);
+  b.off_hb = part(4);
+  b.off_bpd = part(A);
+  b.off_bv1 = part(hidden);
+  b.off_wv2 = part(hidden);
+  b.off_wpd = part(2 * HW * A);
+  b.off_wv1 = part(HW * hidden);
+  return b;
+}
+
+namespace {
+// one tile height: the largest staging it holds -- the whole blob, then
+// without wv1, then without wpd too (those then read from L2); the input-row
+// form runs no dense head: the biases and 1x1 head weights only -- its slot
+// plan and issued FLOP.  rows == 0 in the result: the LDS holds none of them
+TowerTiles tower16_tiles(const TowerShape& s, const TowerBlob& b, int rows, bool dbuf) {
+  const int HW = s.H * s.W, n = s.rows_stem ? 1 : 3;
+  const int prefix[3] = {s.rows_stem ? b.off_bpd : b.floats, b.off_wv1, b.off_wpd};
+  int i = 0;
+  while (i < n && tower16_lds_bytes(HW, rows, prefix[i], dbuf) > kTowerLdsMax) ++i;
+  TowerTiles t;
+  if (i == n) return t;
+  t.rows = rows;
+  t.staged_floats = prefix[i];
+  t.wv1_lds = i == 0 && !s.rows_stem;
+  t.wpd_lds = i <= 1 && !s.rows_stem;
+  // border blocks skip the taps past their edge (natural_order: no plan -- bitwise the same outputs)
+  if (!s.natural_order) tower16_slot_plan(s.H, s.W, rows, t.slot_pix, t.skip);
+  // (chess: as self-play runs it, the stem's known-zero input chunks 0-1 skipped)
+  t.issued_flop_per_board = tower16_issued_flop_per_board(HW, rows, s.depth, t.skip, s.rows_stem, 2);
+  return t;
+}
+}  // namespace
+
+TowerLayout tower16_choose_layout(const TowerShape& s) {
+  const int HW = s.H * s.W, rows = tower16_tile_rows(HW);
+  TowerLayout L;
+  L.blob = tower16_blob_offsets(s.depth, HW, s.A, s.hidden);
+  if (s.depth < 1 || s.depth > kTowerMaxDepth || !rows || (s.rows_stem && rows != 128)) return L;
+  for (int db = 1; db >= 0 && !L.ok; --db) {
+    if (!s.rows_stem && !tower16_heads_fit(HW, rows, s.A, s.hidden, db)) continue;
+    L.main = tower16_tiles(s, L.blob, rows, db);
+    L.ok = L.main.rows != 0;
+    L.dbuf = db;
+  }
+  if (!L.ok) return L;
+  L.wv1_xtile = !s.rows_stem && L.dbuf && !L.main.wv1_lds && tower16_wv1_xtile_fits(HW, rows, s.hidden);
+  // dual launches (tower16_dual_kernel has the measurements): boards of 33-48
+  // cells (Connect-4) in 128-row tiles of three may also run 96-row tiles of
+  // two, with a staging and a slot plan of their own (64 rows fewer hold the
+  // whole blob where 128 rows leave wv1 in L2), when a launch holds at most
+  // two boards per CU that the lanes' towers leave each other
+  if (!s.rows_stem && rows == 128 && L.dbuf && tower16_boards_per_tile(HW, 128) == 3 &&
+      tower16_boards_per_tile(HW, 96) == 2 && tower16_heads_fit(HW, 96, s.A, s.hidden, true)) {
+    L.alt = tower16_tiles(s, L.blob, 96, true);
+    if (L.alt.rows) L.alt_max_boards = 2 * std::max(1, s.cus / std::max(1, s.lanes));
+  }
+  return L;
+}
+
 void tower16_stem_pack(const double* w, int e, std::vector<uint16_t>& out) {
   // conv16_pack's fragment layout ([k-step][n-block][term][lane] x 8 fp16) over k = tap*4 + plane
   const int F = 128;
@@ -1479,45 +1551,53 @@ void tower16_stem_pack(const double* w, int e, std::vector<uint16_t>& out) {
     }
 }
 
+// what a tower16_kernel launch is given (launch_tower16, launch_tower16_rows)
+struct TowerLaunch {
+  const TowerNet* net;
+  int staged;  // blob floats in LDS
+  bool dbuf;
+  const Board* boards;  // input: the queue's boards, planes x, or (input-row form) rows / leaves lv
+  const float4* x;
+  const uint4* rows;
+  const int* count;
+  int n_max, H, W, A;
+  float *probs, *values;  // output: the heads', or (input-row form) the head convs' features
+  float4* feat;
+  int first_chunk;
+  unsigned long long* err;
+  hipStream_t s;
+  TowerLeaves lv;
+};
+
 template <int MBT, int NWM, bool ROWS, bool DB>
-static void launch_db(const TowerNet* net, int staged, const Board* boards, const float4* x, const uint4* rows,
-                      const int* count, int n_max, int H, int W, int A, float* probs, float* values, float4* feat,
-                      int first_chunk, unsigned long long* err, hipStream_t s, TowerLeaves lv = {}) {
-  const int bpw = tower16_boards_per_tile(H * W, 16 * MBT);
-  const int grid = (n_max + bpw - 1) / bpw;
-  const size_t bytes = tower16_lds_bytes(H * W, 16 * MBT, staged, DB);
+static void launch_db(const TowerLaunch& a) {
+  const int bpw = tower16_boards_per_tile(a.H * a.W, 16 * MBT);
+  const int grid = (a.n_max + bpw - 1) / bpw;
+  const size_t bytes = tower16_lds_bytes(a.H * a.W, 16 * MBT, a.staged, DB);
   static bool attr = false;
   if (!attr) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tower16_kernel<MBT, NWM, ROWS, DB>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTowerLdsMax);
     attr = true;
   }
-  tower16_kernel<MBT, NWM, ROWS, DB><<<grid, NWM * 256, bytes, s>>>(net, boards, x, rows, count, n_max, H, W, A,
-                                                                    bpw, probs, values, feat, first_chunk, err, lv);
+  tower16_kernel<MBT, NWM, ROWS, DB><<<grid, NWM * 256, bytes, a.s>>>(a.net, a.boards, a.x, a.rows, a.count, a.n_max,
+                                                                      a.H, a.W, a.A, bpw, a.probs, a.values, a.feat,
+                                                                      a.first_chunk, a.err, a.lv);
 }
 template <int MBT, int NWM, bool ROWS>
-static void launch_mbw(const TowerNet* net, int staged, bool dbuf, const Board* boards, const float4* x,
-                       const uint4* rows, const int* count, int n_max, int H, int W, int A, float* probs,
-                       float* values, float4* feat, int first_chunk, unsigned long long* err, hipStream_t s,
-                       TowerLeaves lv = {}) {
-  if (dbuf)
-    launch_db<MBT, NWM, ROWS, true>(net, staged, boards, x, rows, count, n_max, H, W, A, probs, values, feat,
-                                    first_chunk, err, s, lv);
-  else
-    launch_db<MBT, NWM, ROWS, false>(net, staged, boards, x, rows, count, n_max, H, W, A, probs, values, feat,
-                                     first_chunk, err, s, lv);
+static void launch_mbw(const TowerLaunch& a) {
+  a.dbuf ? launch_db<MBT, NWM, ROWS, true>(a) : launch_db<MBT, NWM, ROWS, false>(a);
 }
 
-void launch_tower16(const TowerNet* net, int tile_rows, int alt_rows, int alt_staged, int staged, bool dbuf,
-                    const Board* boards,
-                    const float4* x, const int* count, int n_max, int H, int W, int A, float* probs, float* values,
-                    unsigned long long* err, hipStream_t s) {
+void launch_tower16(const TowerNet* net, const TowerLayout& L, const Board* boards, const float4* x, const int* count,
+                    int n_max, int H, int W, int A, float* probs, float* values, unsigned long long* err,
+                    hipStream_t s) {
   if (n_max <= 0) return;
-  if (tile_rows == 128 && alt_rows == 96 && dbuf) {  // Connect-4: 96- or 128-row tiles by the live count
+  if (L.alt.rows) {  // Connect-4 (128-row tiles double-buffered, 96-row alt): either height by the live count
     const int bpw = tower16_boards_per_tile(H * W, 128), bpw2 = tower16_boards_per_tile(H * W, 96);
     const int grid = (n_max + bpw2 - 1) / bpw2;
-    const size_t bytes = std::max(tower16_lds_bytes(H * W, 128, staged, true),  // the larger of the two layouts
-                                  tower16_lds_bytes(H * W, 96, alt_staged, true));
+    const size_t bytes = std::max(tower16_lds_bytes(H * W, 128, L.main.staged_floats, true),  // the larger of the two
+                                  tower16_lds_bytes(H * W, 96, L.alt.staged_floats, true));
     static bool attr = false;
     if (!attr) {
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tower16_dual_kernel<8, 6, true>),
@@ -1528,34 +1608,33 @@ void launch_tower16(const TowerNet* net, int tile_rows, int alt_rows, int alt_st
                                                              values, err);
     return;
   }
-  if (tile_rows == 192)  // in place only (two 192-row tiles exceed the LDS)
-    launch_db<12, 2, false, false>(net, staged, boards, x, nullptr, count, n_max, H, W, A, probs, values, nullptr, 0,
-                                   err, s);
-  else if (tile_rows == 96)
-    launch_mbw<6, 2, false>(net, staged, dbuf, boards, x, nullptr, count, n_max, H, W, A, probs, values, nullptr, 0,
-                            err, s);
+  const TowerLaunch a{net, L.main.staged_floats, L.dbuf, boards, x, nullptr, count, n_max, H, W, A, probs, values,
+                      nullptr, 0, err, s, {}};
+  if (L.main.rows == 192)  // in place only (two 192-row tiles exceed the LDS)
+    launch_db<12, 2, false, false>(a);
+  else if (L.main.rows == 96)
+    launch_mbw<6, 2, false>(a);
   else
-    launch_mbw<8, 2, false>(net, staged, dbuf, boards, x, nullptr, count, n_max, H, W, A, probs, values, nullptr, 0,
-                            err, s);
+    launch_mbw<8, 2, false>(a);
 }
 
-void launch_tower16_rows(const TowerNet* net, int tile_rows, int staged, bool dbuf, const void* rows,
-                         int first_chunk, const int* count, int n_max, int H, int W, float4* feat,
-                         unsigned long long* err, hipStream_t s, const TowerLeaves* leaves) {
-  if (n_max <= 0 || tile_rows != 128) return;
+void launch_tower16_rows(const TowerNet* net, const TowerLayout& L, const void* rows, int first_chunk,
+                         const int* count, int n_max, int H, int W, float4* feat, unsigned long long* err,
+                         hipStream_t s, const TowerLeaves* leaves) {
+  if (n_max <= 0 || L.main.rows != 128) return;
   // the leaves' planes are built for the self-play stem (planes 64-127)
   const TowerLeaves lv = leaves && first_chunk == 2 ? *leaves : TowerLeaves{};
+  const TowerLaunch a{net, L.main.staged_floats, L.dbuf, nullptr, nullptr, static_cast<const uint4*>(rows), count,
+                      n_max, H, W, 0, nullptr, nullptr, feat, first_chunk == 2 ? 2 : 0, err, s, lv};
   // a launch of fewer than 512 boards (chess self-play: 128 per lane) in
   // 2-board tiles would hold under a quarter of the 256 CUs: one board per
   // 64-row tile then (MI355X has 256 CUs; the same sums, bitwise), 8 waves of
   // 2 blocks.  (16 waves of one block, four per SIMD: 1.16 M against 1.55 M
   // expansions/s, profiles/r5/ab_chess.txt)
   if (n_max < 512)
-    launch_mbw<4, 2, true>(net, staged, dbuf, nullptr, nullptr, static_cast<const uint4*>(rows), count, n_max, H, W,
-                           0, nullptr, nullptr, feat, first_chunk == 2 ? 2 : 0, err, s, lv);
+    launch_mbw<4, 2, true>(a);
   else
-    launch_mbw<8, 2, true>(net, staged, dbuf, nullptr, nullptr, static_cast<const uint4*>(rows), count, n_max, H, W,
-                           0, nullptr, nullptr, feat, first_chunk == 2 ? 2 : 0, err, s, lv);
+    launch_mbw<8, 2, true>(a);
 }
 
 }  // namespace az

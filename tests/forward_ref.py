@@ -238,12 +238,19 @@ def layouts():
     for it (built against libaz.so and run once per process)."""
     args = [str(v) for c in CASES for v in (c.H, c.W, action_space(c), c.depth, c.hidden)]
     with tempfile.TemporaryDirectory() as tmp:
-        exe = os.path.join(tmp, "tower_layout_check")
-        subprocess.run(["g++", "-O1", "-std=c++17", "-o", exe, os.path.join(REPO, "tests", "native", "tower_layout_check.cpp"),
-                        os.path.join(LIB, "libaz.so"), f"-Wl,-rpath,{LIB}"], check=True)
-        rows = json.loads(subprocess.run([exe] + args, check=True, capture_output=True, text=True).stdout)
+        rows = json.loads(run_layout_check(tmp, args))
     assert len(rows) == len(CASES)
     return {c.name: r for c, r in zip(CASES, rows)}
+
+
+def run_layout_check(tmp, args):
+    """Builds tests/native/tower_layout_check.cpp in tmp against libaz.so and
+    the library's layout header, runs it with args -> its stdout."""
+    exe = os.path.join(tmp, "tower_layout_check")
+    subprocess.run(["g++", "-O1", "-std=c++17", "-I", os.path.join(REPO, "custom-alphazero_amd", "csrc"), "-o", exe,
+                    os.path.join(REPO, "tests", "native", "tower_layout_check.cpp"),
+                    os.path.join(LIB, "libaz.so"), f"-Wl,-rpath,{LIB}"], check=True)
+    return subprocess.run([exe] + args, check=True, capture_output=True, text=True).stdout
 
 
 @functools.lru_cache(maxsize=None)

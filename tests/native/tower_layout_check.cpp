@@ -1,114 +1,112 @@
-// States the layout the one-launch tower gets for a network, from libaz.so's
-// own host functions (az::tower16_*), walking load_network's order of
-// preference (csrc/az_engine.hip): the tile height of the board, double-
-// buffered before in place, and per layout the largest staging of the
-// small-weight blob that the LDS holds (the whole blob, then without wv1,
-// then without wpd too); the wv1 DMA into X's tile; the slot plan; the dual
-// launch's 96-row tiles with a staging and a plan of their own.
-//
-// Two things cannot be read from the library and are restated here: the
-// blob's three prefixes (load_network's `put` order, every part padded to a
-// multiple of four floats) and the LDS budget kTowerLdsMax (csrc/az_nn.h).
-// tests/test_forward_layouts_gpu.py pins what the restatement leads to -- tile
-// rows, boards per tile and the plan's skips -- against the engine's own
-// issued_flop_per_board.
-//
-// argv: groups of H W A depth hidden.  One JSON object per group on stdout.
-#include <cstddef>
+// States the layout the one-launch tower gets for a Connect-N network: what
+// libaz.so's own chooser az::tower16_choose_layout (csrc/az_tower16.hip; the
+// function load_network, the launchers and the stats read) returns.  Only
+// presentation is added here: the name of the slot plan's form and the FLOP
+// of the same tiles without a plan.  CUs and lanes are fixed (256, 1): the
+// dual launch's threshold is not printed.
+// argv: groups of H W A depth hidden -> one JSON object per group.
+// --sweep: every Connect-N shape the tower takes (H, W >= 2, HW <= 128; A = W
+// or HW; depth 1, 4, 16; hidden 1, 64, 255, 256), each chosen layout checked
+// against the library's other tower16_* functions ->
+// {"shapes", "not_ok": [shapes without a layout], "failures": [shape + what]}.
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <string>
 #include <vector>
 
-namespace az {
-void tower16_slot_plan(int H, int W, int tile_rows, std::vector<int>& slot_pix, int skip[2]);
-double tower16_issued_flop_per_board(int HW, int tile_rows, int depth, const int skip[2], bool rows_stem,
-                                     int stem_chunks);
-int tower16_tile_rows(int HW);
-int tower16_boards_per_tile(int HW, int tile_rows);
-size_t tower16_lds_bytes(int HW, int tile_rows, int staged_floats, bool dbuf);
-bool tower16_heads_fit(int HW, int tile_rows, int A, int hidden, bool dbuf);
-bool tower16_wv1_xtile_fits(int HW, int tile_rows, int hidden);
-}  // namespace az
+#include "az_tower_layout.h"
 
 namespace {
-const size_t kLdsMax = 160 * 1024;  // csrc/az_nn.h kTowerLdsMax
-const int F = 128;
+using az::TowerLayout;
+using az::TowerTiles;
 
-int pad4(int n) { return (n + 3) & ~3; }
-
-struct Plan {
-  const char* form;
-  int skipped;  // block-taps over both M halves
-  double flop, flop_natural;
-};
-
-Plan plan_of(int H, int W, int tr, int depth) {
-  std::vector<int> pix;
-  int skip[2] = {0, 0};
+TowerLayout layout_of(int H, int W, int A, int depth, int hidden) {
+  az::TowerShape s;
+  s.H = H, s.W = W, s.A = A, s.depth = depth, s.hidden = hidden, s.cus = 256, s.lanes = 1;
+  return az::tower16_choose_layout(s);
+}
+double natural_flop(const TowerTiles& t, int HW, int depth) {
   const int none[2] = {0, 0};
-  az::tower16_slot_plan(H, W, tr, pix, skip);
-  if (pix.empty()) skip[0] = skip[1] = 0;  // load_network uploads no plan: natural order
-  int skipped = 0;
-  for (int h = 0; h < 2; ++h) skipped += __builtin_popcount(skip[h]);
-  // four border blocks (top, bottom | left, right) skip 3 taps each, top | bottom alone 6
-  const char* form = pix.empty() ? "none" : skipped == 12 ? "four_borders" : skipped == 6 ? "top_bottom" : "other";
-  return {form, skipped, az::tower16_issued_flop_per_board(H * W, tr, depth, skip, false, 2),
-          az::tower16_issued_flop_per_board(H * W, tr, depth, none, false, 2)};
+  return az::tower16_issued_flop_per_board(HW, t.rows, depth, none, false, 2);
+}
+// wv1, wpd, plan, skipped, flop, flop_natural of one tile height, each key with `pre` in front
+void print_tiles(const TowerTiles& t, const char* pre, bool xtile, int HW, int depth) {
+  // skipped block-taps over both M halves: four border blocks (top, bottom | left, right) skip 3 taps each,
+  // top | bottom alone 6
+  const int k = __builtin_popcount(t.skip[0]) + __builtin_popcount(t.skip[1]);
+  const char* form = t.slot_pix.empty() ? "none" : k == 12 ? "four_borders" : k == 6 ? "top_bottom" : "other";
+  printf(", \"%swv1\": \"%s\", \"%swpd\": \"%s\", \"%splan\": \"%s\", \"%sskipped\": %d, \"%sflop\": %.17g, "
+         "\"%sflop_natural\": %.17g",
+         pre, xtile ? "xtile" : t.wv1_lds ? "lds" : "l2", pre, t.wpd_lds ? "lds" : "l2", pre, form, pre, k, pre,
+         t.issued_flop_per_board, pre, natural_flop(t, HW, depth));
+}
+
+// what one tile height of a chosen layout gets wrong; "" when its invariants hold
+std::string fault_of(const TowerLayout& L, const TowerTiles& t, bool dbuf, int H, int W, int A, int depth, int hidden) {
+  const int HW = H * W, bpt = az::tower16_boards_per_tile(HW, t.rows), staged = t.staged_floats;
+  if (az::tower16_lds_bytes(HW, t.rows, staged, dbuf) > az::kTowerLdsMax) return "lds";
+  if (!az::tower16_heads_fit(HW, t.rows, A, hidden, dbuf)) return "heads";
+  if (staged != L.blob.floats && staged != L.blob.off_wv1 && staged != L.blob.off_wpd) return "prefix";
+  if (t.wv1_lds != (staged == L.blob.floats) || t.wpd_lds != (staged >= L.blob.off_wv1)) return "staging flags";
+  if (t.wv1_lds && !t.wpd_lds) return "wv1 without wpd";
+  const double flop = t.issued_flop_per_board, natural = natural_flop(t, HW, depth);
+  if (t.slot_pix.empty()) return t.skip[0] || t.skip[1] ? "skips without a plan" : flop != natural ? "flop" : "";
+  if ((int)t.slot_pix.size() != t.rows) return "plan size";
+  std::vector<int> seen(bpt * HW, 0);  // every pixel of the tile's boards once, every other slot an empty word
+  for (int v : t.slot_pix) {
+    const int b = v >> 16, y = (v >> 8) & 255, x = v & 255;
+    if (y != 127 && (b < 0 || b >= bpt || y >= H || x >= W || seen[b * HW + y * W + x]++)) return "plan pixel";
+  }
+  for (int c : seen)
+    if (!c) return "plan misses a pixel";
+  return flop < natural ? "" : "flop";
+}
+
+int sweep() {
+  int shapes = 0;
+  std::string not_ok, failures;
+  for (int H = 2; H <= 64; ++H)
+    for (int W = 2; H * W <= 128; ++W)
+      for (int A : {W, H * W})
+        for (int depth : {1, 4, 16})
+          for (int hidden : {1, 64, 255, 256}) {
+            const TowerLayout L = layout_of(H, W, A, depth, hidden);
+            char at[96];
+            ++shapes;
+            snprintf(at, sizeof at, "[%d, %d, %d, %d, %d", H, W, A, depth, hidden);
+            auto add = [&](std::string& list, const std::string& end) { list += (list.empty() ? "" : ", ") + (at + end); };
+            std::string fault = L.ok ? fault_of(L, L.main, L.dbuf, H, W, A, depth, hidden) : "";
+            if (fault.empty() && L.alt.rows) fault = fault_of(L, L.alt, true, H, W, A, depth, hidden);
+            if (!L.ok) add(not_ok, "]");
+            if (!fault.empty()) add(failures, ", \"" + fault + "\"]");
+          }
+  printf("{\"shapes\": %d, \"not_ok\": [%s], \"failures\": [%s]}\n", shapes, not_ok.c_str(), failures.c_str());
+  return 0;
 }
 }  // namespace
 
 int main(int argc, char** argv) {
+  if (argc == 2 && !strcmp(argv[1], "--sweep")) return sweep();
   if ((argc - 1) % 5) {
-    fprintf(stderr, "usage: tower_layout_check (H W A depth hidden)...\n");
+    fprintf(stderr, "usage: tower_layout_check (H W A depth hidden)... | --sweep\n");
     return 2;
   }
   printf("[");
   for (int a = 1; a + 4 < argc; a += 5) {
     const int H = atoi(argv[a]), W = atoi(argv[a + 1]), A = atoi(argv[a + 2]), depth = atoi(argv[a + 3]),
               hidden = atoi(argv[a + 4]), HW = H * W;
-    // the blob (load_network): b1, b2 [depth][F], stem bias [F], wpc [F][2], wvc [F], hb [4], bpd [A],
-    // bv1 [hidden], wv2 [hidden], then wpd [2HW][A] and wv1 [HW][hidden]
-    const int off_wpd = 2 * pad4(depth * F) + pad4(F) + pad4(2 * F) + pad4(F) + 4 + pad4(A) + 2 * pad4(hidden);
-    const int off_wv1 = off_wpd + pad4(2 * HW * A), blob = off_wv1 + pad4(HW * hidden);
-    const int prefix[3] = {blob, off_wv1, off_wpd};
-    const int tr = az::tower16_tile_rows(HW);
-    bool found = false, db = false;
-    int staged = -1;
-    if (depth >= 1 && depth <= 16 && hidden <= 256)  // az_engine_create: use_tower
-      for (int li = 0; li < 2 && !found; ++li) {
-        const bool d = li == 0;
-        if (!tr || !az::tower16_heads_fit(HW, tr, A, hidden, d)) continue;
-        for (int i = 0; i < 3 && !found; ++i)
-          if (az::tower16_lds_bytes(HW, tr, prefix[i], d) <= kLdsMax) {
-            found = true;
-            db = d;
-            staged = i;
-          }
-      }
+    const TowerLayout L = layout_of(H, W, A, depth, hidden);
     printf("%s{\"H\": %d, \"W\": %d, \"A\": %d, \"depth\": %d, \"hidden\": %d, \"tower\": %d", a > 1 ? ",\n" : "", H, W, A,
-           depth, hidden, (int)found);
-    if (found) {
-      const int bpt = az::tower16_boards_per_tile(HW, tr);
-      const bool xtile = db && staged != 0 && az::tower16_wv1_xtile_fits(HW, tr, hidden);
-      const Plan p = plan_of(H, W, tr, depth);
-      printf(", \"tile_rows\": %d, \"boards\": %d, \"pads\": %d, \"dbuf\": %d, \"wv1\": \"%s\", \"wpd\": \"%s\", "
-             "\"plan\": \"%s\", \"skipped\": %d, \"flop\": %.17g, \"flop_natural\": %.17g",
-             tr, bpt, tr - bpt * HW, (int)db, staged == 0 ? "lds" : xtile ? "xtile" : "l2", staged <= 1 ? "lds" : "l2",
-             p.form, p.skipped, p.flop, p.flop_natural);
-      const bool dual = tr == 128 && db && bpt == 3 && az::tower16_boards_per_tile(HW, 96) == 2 &&
-                        az::tower16_heads_fit(HW, 96, A, hidden, true);
-      printf(", \"dual\": %d", (int)dual);
-      if (dual) {
-        int alt = -1;
-        for (int i = 0; i < 3 && alt < 0; ++i)
-          if (az::tower16_lds_bytes(HW, 96, prefix[i], true) <= kLdsMax) alt = i;
-        const Plan q = plan_of(H, W, 96, depth);
-        // (the X-tile DMA of wv1 is the primary tile height's alone: here staged or from L2)
-        printf(", \"alt_wv1\": \"%s\", \"alt_wpd\": \"%s\", \"alt_plan\": \"%s\", \"alt_skipped\": %d, "
-               "\"alt_flop\": %.17g, \"alt_flop_natural\": %.17g",
-               alt < 0 ? "none" : alt == 0 ? "lds" : "l2", alt < 0 ? "none" : alt <= 1 ? "lds" : "l2", q.form, q.skipped,
-               q.flop, q.flop_natural);
-      }
+           depth, hidden, (int)L.ok);
+    if (L.ok) {
+      const int bpt = az::tower16_boards_per_tile(HW, L.main.rows);
+      printf(", \"tile_rows\": %d, \"boards\": %d, \"pads\": %d, \"dbuf\": %d", L.main.rows, bpt, L.main.rows - bpt * HW,
+             (int)L.dbuf);
+      print_tiles(L.main, "", L.wv1_xtile, HW, depth);
+      printf(", \"dual\": %d", (int)(L.alt.rows != 0));
+      // (the X-tile DMA of wv1 is the main tiles' alone: the alt tiles have it staged or from L2)
+      if (L.alt.rows) print_tiles(L.alt, "alt_", false, HW, depth);
     }
     printf("}");
   }

@@ -1,8 +1,12 @@
 """The forward tests' case table (tests/forward_ref.py), checked with no GPU:
 the table reaches every tower layout load_network can choose (by the library's
-own chooser functions, tests/native/tower_layout_check.cpp), and every case's
+own chooser, az::tower16_choose_layout through tests/native/tower_layout_check.cpp),
+the chooser keeps its invariants over every board the tower takes, and every case's
 weights are lively and its reference separates honest float32 arithmetic from
 the mildest mutant by 64x.  tests/test_forward_layouts_gpu.py runs the cases."""
+import json
+import os
+
 import numpy as np
 import pytest
 
@@ -73,6 +77,23 @@ def test_case_table_reaches_every_tower_layout():
         assert (r["tile_rows"], r["boards"], r["dbuf"], r["wv1"], r["wpd"], r["plan"]) == e, (name, r)
     for c, r in rows:  # a plan only ever removes work
         assert r["flop"] <= r["flop_natural"] and (r["flop"] < r["flop_natural"]) == (r["plan"] != "none"), r
+
+
+@pytest.mark.skipif(not fr.have_lib(), reason="libaz.so not built")
+def test_layout_sweep_keeps_the_choosers_invariants(tmp_path):
+    """Every Connect-N shape the tower takes (390 boards of H, W >= 2 and
+    HW <= 128, A = W or HW, depth 1 / 4 / 16, hidden 1 / 64 / 255 / 256): each
+    chosen layout fits the LDS and the heads' scratch, stages one of the three
+    blob prefixes, and its slot plans hold every pixel once and only remove
+    work.  The shapes without a layout are those of the golden list, which the
+    restating check program of the commit before the chooser existed produced
+    over the same sweep: none -- the per-layer fallback is not reachable for
+    4 input planes within the engine's limits."""
+    out = json.loads(fr.run_layout_check(str(tmp_path), ["--sweep"]))
+    assert out["shapes"] == 390 * 2 * 3 * 4
+    assert out["failures"] == []
+    with open(os.path.join(fr.REPO, "tests", "golden", "tower_layout_not_ok.json")) as f:
+        assert out["not_ok"] == json.load(f)
 
 
 def test_old_weights_leave_the_value_head_dead():
