@@ -445,9 +445,52 @@ __device__ __forceinline__ void select_body(const GameCfg& g, const TreeDev& t, 
   leaf_tail(g, t, c, s, E, path, depth, status, b);
 }
 
+// Reductions over a group of L lanes in registers.  group_partner<K> is the
+// value held by this lane's partner of step K: steps 0-3 are DPP moves inside
+// a 16-lane row (quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror,
+// row_mirror -- no LDS round trip, where a __shfl_xor is a ds_bpermute per
+// 32-bit word); steps 4 and 5 cross rows and stay shuffles.  A mirror pairs a
+// lane with one of the other half, which stands for that whole half only once
+// the steps before it have run: the steps go in ascending order.  Every lane
+// of a group ends with the group's result when the combining rule does not
+// depend on the order of its operands (an integer sum, a maximum over a
+// total order).
+template <int K>
+__device__ __forceinline__ int group_partner(int v) {
+  static_assert(K >= 0 && K < 6, "one wave");
+  if constexpr (K == 0) return __builtin_amdgcn_mov_dpp(v, 0xB1, 0xF, 0xF, true);
+  else if constexpr (K == 1) return __builtin_amdgcn_mov_dpp(v, 0x4E, 0xF, 0xF, true);
+  else if constexpr (K == 2) return __builtin_amdgcn_mov_dpp(v, 0x141, 0xF, 0xF, true);
+  else if constexpr (K == 3) return __builtin_amdgcn_mov_dpp(v, 0x140, 0xF, 0xF, true);
+  else return __shfl_xor(v, 1 << K);
+}
+template <int K>
+__device__ __forceinline__ double group_partner(double v) {
+  return __hiloint2double(group_partner<K>(__double2hiint(v)), group_partner<K>(__double2loint(v)));
+}
+template <int L, int K = 0>
+__device__ __forceinline__ int group_sum(int v) {
+  if constexpr ((1 << K) < L) return group_sum<L, K + 1>(v + group_partner<K>(v));
+  else return v;
+}
+// first maximum of (v, i) over the group; NAN_MAX: in np.argmax's order
+// (argmax_before), else `>` with the lower index on ties
+template <int L, bool NAN_MAX, int K = 0>
+__device__ __forceinline__ void group_argmax(double& v, int& i) {
+  if constexpr ((1 << K) < L) {
+    const double ov = group_partner<K>(v);
+    const int oi = group_partner<K>(i);
+    // (selects, not branches: `|` and `&` keep the step free of exec masking)
+    const bool take = NAN_MAX ? argmax_before(ov, oi, v, i) : bool((ov > v) | ((ov == v) & (oi < i)));
+    v = take ? ov : v;
+    i = take ? oi : i;
+    group_argmax<L, NAN_MAX, K + 1>(v, i);
+  }
+}
+
 // Group descent: a game is a group of L lanes (L = next power of two >= A).
 // Lane j loads edge j (contiguous, one 32-byte record per lane), the group
-// sums N and takes the first-maximum UCB by shuffles -- the same float64
+// sums N and takes the first-maximum UCB in registers -- the same float64
 // expressions as the serial loop, so the chosen edge is identical.
 // SHAPE 1: Connect-4 (6x7, n = 4, gravity) with the compile-time one-word
 // play (play_c64); 0: any shape through play_bb's runtime masks.
@@ -485,10 +528,17 @@ __device__ __forceinline__ void select_group_body(const GameCfg& g, const TreeDe
   int32_t* path = t.path + (size_t)s * g.max_depth;
   int depth = 0, status = kOngoing;
   // below the root, the children's visits sum to the parent edge's N - 1 (the
-  // first visit expanded the node), so sqrt(sum) is fetched before the
-  // children's edges arrive instead of after them: one dependent load per
-  // level instead of two
+  // first visit expanded the node), so pow(sum, 0.5) is requested with the
+  // children's edges instead of after them
   int sum_next = -1;
+  // A level's loads are issued a level ahead, as soon as the choice above it
+  // is known and before that level's play: lane j's edge (e) and the table
+  // entry (sq), the root's edges before the loop.
+  Edge e = {};
+  double sq = 0.0;
+  if (j < cnt) e = E[first + j];
+  // (a return waits for them first: the empty asm takes what may be in flight)
+  auto drain = [&] { asm volatile("" : : "v"(e.W), "v"(e.N), "v"(sq)); };
 #ifdef AZ_SEL_STAMPS
   __builtin_amdgcn_s_waitcnt(0);
   if (j == 0) AZ_SEL_STAMP(s, 11);  // root loads done, loop entry
@@ -498,24 +548,11 @@ __device__ __forceinline__ void select_group_body(const GameCfg& g, const TreeDe
     ph_t = wall_clock64();
 #endif
     const bool mine = j < cnt;
-    double sq;
-    int sum;
-    if (sum_next >= 0) {
-      sum = sum_next;
+    if (sum_next < 0) {  // the root: the sum from its edges, then the table
+      const int sum = group_sum<L>(mine ? e.N : 0);
       if (sum >= g.pow_len) {
         if (j == 0) flag_error(t, kErrPow);
-        return;
-      }
-      sq = t.powtab[sum];
-    }
-    Edge e;
-    if (mine) e = E[first + j];
-    if (sum_next < 0) {
-      sum = mine ? e.N : 0;
-#pragma unroll
-      for (int off = L / 2; off > 0; off >>= 1) sum += __shfl_xor(sum, off, L);
-      if (sum >= g.pow_len) {
-        if (j == 0) flag_error(t, kErrPow);
+        drain();
         return;
       }
       sq = t.powtab[sum];
@@ -532,6 +569,7 @@ __device__ __forceinline__ void select_group_body(const GameCfg& g, const TreeDe
         row = __shfl(row, 0, L);
         if (row >= t.noise_rows) {
           if (j == 0) flag_error(t, kErrNoise);
+          drain();
           return;
         }
         if (mine) dj = t.noise_in[((size_t)s * t.noise_rows + row) * g.A + j];
@@ -558,15 +596,7 @@ __device__ __forceinline__ void select_group_body(const GameCfg& g, const TreeDe
         best_v = q + u;
         best = j;
       }
-#pragma unroll
-      for (int off = L / 2; off > 0; off >>= 1) {
-        const double ov = __shfl_xor(best_v, off, L);
-        const int oj = __shfl_xor(best, off, L);
-        if (argmax_before(ov, oj, best_v, best)) {
-          best_v = ov;
-          best = oj;
-        }
-      }
+      group_argmax<L, true>(best_v, best);
     } else {
       if (mine) {
         const double q = e.N ? e.W / (double)e.N : 0.0;
@@ -574,25 +604,28 @@ __device__ __forceinline__ void select_group_body(const GameCfg& g, const TreeDe
         best_v = q + u;
         best = j;
       }
-#pragma unroll
-      for (int off = L / 2; off > 0; off >>= 1) {
-        const double ov = __shfl_xor(best_v, off, L);
-        const int oj = __shfl_xor(best, off, L);
-        if (ov > best_v || (ov == best_v && oj < best)) {  // np.argmax: first maximum
-          best_v = ov;
-          best = oj;
-        }
-      }
+      group_argmax<L, false>(best_v, best);  // np.argmax: first maximum
     }
     if (depth >= g.max_depth) {
       if (j == 0) flag_error(t, kErrPath);
+      drain();
       return;
     }
-    const int action = __shfl(mine ? (int)(e.action & kActMask) : 0, best, L);
+    // the winner's fields, three permutes issued together (action and child_n share a word)
+    const int act_n = __shfl(mine ? ((e.action & kActMask) << 16) | (uint16_t)e.child_n : 0, best, L);
     const int child = __shfl(mine ? e.child : 0, best, L);
-    const int child_n = __shfl(mine ? (int)e.child_n : 0, best, L);
     sum_next = __shfl(mine ? e.N : 0, best, L) - 1;
+    const int action = act_n >> 16, child_n = (int16_t)act_n;
     AZ_SEL_PHASE(ph_reduce);
+    if (child_n > 0) {  // the next level's loads, ahead of this level's play
+      if (sum_next >= g.pow_len) {
+        if (j == 0) flag_error(t, kErrPow);
+        drain();
+        return;
+      }
+      sq = t.powtab[sum_next];
+      if (j < child_n) e = E[child + j];
+    }
     if (j == 0) path[depth] = first + best;
     ++depth;
     if constexpr (SHAPE == 1) status = play_c64<6, 7, 4>(b, action);
@@ -600,6 +633,7 @@ __device__ __forceinline__ void select_group_body(const GameCfg& g, const TreeDe
     AZ_SEL_PHASE(ph_play);
     if (status < 0) {
       if (j == 0) flag_error(t, kErrIllegal);
+      drain();
       return;
     }
     first = child;

@@ -7,7 +7,9 @@ last select launch of a move: 0 entry, 1 game_id read, 11 root loads done (masks
 root board), 2 end of descent,
 3 after the two per-wave stats atomics, 4 after the eval-queue claim + stores,
 5 after the cache probe, 6 end (dedup-table claim for misses); per-level sums: 8 loads, 9 UCB +
-reductions, 10 play.
+reductions, 10 play.  Since the descent requests a level's edges before the
+level above's play (profiles/select/), each stamp's s_waitcnt 0 puts that
+round trip into "play" and leaves "loads" the root's visit sum and table entry.
 Usage: AZ_LIB_PATH=profiles/ab_libs/selst/libaz.so python profiles/sel_stamps.py [--synth]"""
 import ctypes
 import os
