@@ -12,7 +12,8 @@
 //            the leaf; terminal leaves back up get_result's value, the rest
 //            join the eval queue
 //   encode   one workgroup per queued board: Board.full_state planes straight
-//            into the network input (padded to 128 channels)
+//            into the network input (padded to 128 channels); for a host
+//            evaluator (AZ_EVAL_HOST) the dense 118-plane rows it reads
 //   expand   one wave per queued board: priors = probs[mask] renormalised in
 //            action order (float32 pairwise sum) and zipped positionally with
 //            python-chess's move order (mcts.py:147-160), edges allocated, backup
@@ -831,6 +832,44 @@ __global__ __launch_bounds__(256) void encode_queue_kernel(CCfg g, CTree t, void
   }
 }
 
+// AZ_EVAL_HOST: Board.full_state of the queued leaves as a host evaluator
+// reads it, dense rows [q][8][8][118] f32 with every plane present -- the
+// history planes 0-83 the self-play stem skips are written (zeros), nothing
+// is padded.  The history form is encode_queue_kernel's.  Consecutive
+// threads write consecutive floats.
+__global__ __launch_bounds__(256) void encode_host_kernel(CCfg g, CTree t, float* __restrict__ x) {
+  __shared__ Pos sp[2];
+  __shared__ float feat[6];
+  __shared__ int initial;
+  const int n = min(*t.eval_count, g.slots);
+  for (int b = blockIdx.x; b < n; b += gridDim.x) {
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const int s = t.eval_slot[b];
+      sp[0] = start_pos();
+      sp[1] = load_pos(t.leaf[s]);
+      initial = t.path_len[s] == 0 && t.initial[s];
+      float f[6];
+      state_feats(sp[1], f);
+      for (int i = 0; i < 6; ++i) feat[i] = f[i];
+    }
+    __syncthreads();
+    float f[6];
+    for (int i = 0; i < 6; ++i) f[i] = feat[i];
+    float* o = x + (size_t)b * 64 * AZ_CHESS_PLANES;
+    for (int e = threadIdx.x; e < 64 * AZ_CHESS_PLANES; e += blockDim.x) {
+      const int pix = e / AZ_CHESS_PLANES, k = e - pix * AZ_CHESS_PLANES;
+      float val = 0.f;
+      if (k >= 84) {  // planes 84-117 (full_state4 takes four from a multiple of 4 >= 64)
+        float v[4];
+        full_state4(sp[0], sp[1], initial != 0, f, pix, k & ~3, v);
+        val = (k & 2) ? ((k & 1) ? v[3] : v[2]) : ((k & 1) ? v[1] : v[0]);
+      }
+      o[e] = val;
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void synth_kernel(CCfg g, CTree t, float* probs, float* values) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= *t.eval_count) return;
@@ -1083,12 +1122,63 @@ struct az_chess_engine {
   int16_t* tree_pol_a = nullptr;
   double* tree_pol_p = nullptr;
   az_chess_pos* tree_roots = nullptr;
+  // AZ_EVAL_HOST: the callback and its pinned staging buffers (slots leaves)
+  az_eval_fn host_fn = nullptr;
+  void* host_user = nullptr;
+  float* host_x = nullptr;
+  float* host_p = nullptr;
+  float* host_v = nullptr;
+  int32_t* host_n = nullptr;
+  // a host evaluator failed mid-simulation (AZ_E_CALLBACK): the leaves it
+  // selected were never expanded, so the trees are one simulation short;
+  // searching refuses until az_chess_selfplay_begin or az_chess_tree_reset
+  bool broken = false;
 };
 
 namespace {
 
 int check_errors(az_chess_engine* e) {
   return az::device_error_status(e->t.stats, {"(raise az_chess_config.arena_edges)", ""});
+}
+
+// AZ_EVAL_HOST: the queued leaves' full_state planes to the host, the callback
+// (the reference's self.model(np.expand_dims(board.full_state, 0)),
+// mcts.py:130-137, here over every leaf of the lane's simulation at once), its
+// outputs back to the lane's evaluator slices.  Synchronous on the lane's
+// stream: after the first wait the select launch is complete, so the count
+// and the planes are final and the fused expand has read the previous
+// simulation's probs / values; after the last one the staging buffers are
+// free for the next lane.
+int host_evaluate(az_chess_engine* e, CLane& L) {
+  hipStream_t s = L.stream;
+  const int S = L.g.slots;
+  constexpr size_t kRow = (size_t)64 * AZ_CHESS_PLANES;
+  encode_host_kernel<<<std::min(S, 2048), 256, 0, s>>>(L.g, L.t, L.x);
+  AZ_HIP(hipGetLastError());
+  AZ_HIP(hipMemcpyAsync(e->host_n, L.t.eval_count, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  AZ_HIP(hipStreamSynchronize(s));
+  const int n = *e->host_n;
+  if (n <= 0) return 0;
+  if (n > S) return az::fail_abi(AZ_E_DEVICE, "host evaluator: leaf count past the lane's slots");
+  AZ_HIP(hipMemcpyAsync(e->host_x, L.x, (size_t)n * kRow * sizeof(float), hipMemcpyDeviceToHost, s));
+  AZ_HIP(hipStreamSynchronize(s));
+  if (e->host_fn(e->host_user, e->host_x, n, e->host_p, e->host_v) != 0)
+    return az::fail_abi(AZ_E_CALLBACK, "the host evaluator returned an error");
+  AZ_HIP(hipMemcpyAsync(L.probs, e->host_p, (size_t)n * AZ_CHESS_ACTIONS * sizeof(float), hipMemcpyHostToDevice, s));
+  AZ_HIP(hipMemcpyAsync(L.values, e->host_v, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s));
+  AZ_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int ready_to_search(az_chess_engine* e) {
+  if (e->broken)
+    return az::fail_abi(AZ_E_STATE, "a host evaluator error interrupted a simulation: the trees are incomplete "
+                                    "until az_chess_selfplay_begin or az_chess_tree_reset");
+  if (e->cfg.evaluator == AZ_EVAL_NETWORK && !e->net.ready)
+    return az::fail_abi(AZ_E_STATE, "network evaluator selected but az_chess_engine_set_weights was not called");
+  if (e->cfg.evaluator == AZ_EVAL_HOST && !e->host_fn)
+    return az::fail_abi(AZ_E_STATE, "host evaluator selected but az_chess_engine_set_evaluator was not called");
+  return 0;
 }
 
 int simulate(az_chess_engine* e, CLane& L) {
@@ -1126,6 +1216,12 @@ int simulate(az_chess_engine* e, CLane& L) {
     az::launch_forward(e->net, L.x, L.t.eval_count, S, 8, 8, AZ_CHESS_ACTIONS, L.act[0], L.act[1],
                        L.act[2], L.probs, L.values, s, L.timer.enabled ? &L.timer : nullptr, nullptr,
                        kStemFirstChunk, tower ? &lv : nullptr);
+  } else if (L.g.evaluator == AZ_EVAL_HOST) {
+    L.pending_expand = false;  // (the select launch ran it; none is owed if the callback fails)
+    if (int rc = host_evaluate(e, L)) {
+      e->broken = true;
+      return rc;
+    }
   } else {
     synth_kernel<<<(S + 255) / 256, 256, 0, s>>>(L.g, L.t, L.probs, L.values);
   }
@@ -1196,7 +1292,7 @@ int make_lane(az_chess_engine* e, CLane* L, int first, int n) {
   t.epoch = 0;
   L->cache = e->cache;
   L->t = t;
-  if (e->x) L->x = e->x + f * 64 * 128;
+  if (e->x) L->x = e->x + f * 64 * (e->g.evaluator == AZ_EVAL_HOST ? AZ_CHESS_PLANES : 128);
   for (int i = 0; i < 3; ++i) L->act[i] = e->act[i] ? e->act[i] + f * 64 * 128 : nullptr;
   L->probs = e->probs + f * AZ_CHESS_ACTIONS;
   L->values = e->values + f;
@@ -1213,7 +1309,7 @@ int az_chess_engine_create(int device, const az_chess_config* cfg, az_chess_engi
   if (!cfg || !out) return az::fail_abi(AZ_E_INVALID, "null argument");
   const az_chess_config& c = *cfg;
   if (c.slots < 1 || c.mcts_iterations < 1) return az::fail_abi(AZ_E_INVALID, "slots and mcts_iterations must be >= 1");
-  if (c.evaluator != AZ_EVAL_NETWORK && c.evaluator != AZ_EVAL_SYNTHETIC)
+  if (c.evaluator != AZ_EVAL_NETWORK && c.evaluator != AZ_EVAL_SYNTHETIC && c.evaluator != AZ_EVAL_HOST)
     return az::fail_abi(AZ_E_INVALID, "unknown evaluator");
   if (c.evaluator == AZ_EVAL_NETWORK && c.filters != 128)
     return az::fail_abi(AZ_E_INVALID, "network evaluator supports filters == 128 (ConfigModel.filters)");
@@ -1290,6 +1386,15 @@ int az_chess_engine_create(int device, const az_chess_config* cfg, az_chess_engi
     for (int i = 0; i < 3; ++i)
       if ((rc = e->mem.alloc(&e->act[i], S * 64 * 128, false))) return cleanup(rc);
   }
+  if (c.evaluator == AZ_EVAL_HOST) {
+    // the leaves' dense rows [S][64][118] and their pinned host copy, the callback's outputs
+    if ((rc = e->mem.alloc(&e->x, S * 64 * AZ_CHESS_PLANES, false))) return cleanup(rc);
+    if (hipHostMalloc(&e->host_x, S * 64 * AZ_CHESS_PLANES * sizeof(float), hipHostMallocDefault) != hipSuccess ||
+        hipHostMalloc(&e->host_p, S * AZ_CHESS_ACTIONS * sizeof(float), hipHostMallocDefault) != hipSuccess ||
+        hipHostMalloc(&e->host_v, S * sizeof(float), hipHostMallocDefault) != hipSuccess ||
+        hipHostMalloc(&e->host_n, sizeof(int32_t), hipHostMallocDefault) != hipSuccess)
+      return cleanup(az::fail_abi(AZ_E_HIP, "host evaluator staging allocation failed"));
+  }
   t.mt_stride = g.slots;
   // the transposition cache (mcts.py:122-143 on chess boards)
   if (c.cache_log2 < 0 || c.cache_log2 > 28 || (c.cache_log2 > 0 && c.cache_log2 < 4))
@@ -1363,8 +1468,26 @@ int az_chess_engine_destroy(az_chess_engine* e) {
   e->samples.free_all();
   e->mem.free_all();
   if (e->timer_ref) (void)hipEventDestroy(e->timer_ref);
+  for (void* q : {(void*)e->host_x, (void*)e->host_p, (void*)e->host_v, (void*)e->host_n})
+    if (q) (void)hipHostFree(q);
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
+  return 0;
+}
+
+int az_chess_engine_set_evaluator(az_chess_engine* e, az_eval_fn fn, void* user) {
+  if (!e || !fn) return az::fail_abi(AZ_E_INVALID, "null argument");
+  if (e->cfg.evaluator != AZ_EVAL_HOST)
+    return az::fail_abi(AZ_E_STATE, "the engine was not created with AZ_EVAL_HOST");
+  AZ_HIP(hipSetDevice(e->device));
+  int rc;
+  if ((rc = sync_lanes(e))) return rc;
+  e->host_fn = fn;
+  e->host_user = user;
+  if (e->cache.state) {  // cached outputs belong to the previous evaluator
+    AZ_HIP(hipMemset(e->cache.state, 0, ((size_t)e->cache.mask + 1) * sizeof(uint32_t)));
+    AZ_HIP(hipMemset(e->cache.ctl, 0, 4 * sizeof(unsigned long long)));
+  }
   return 0;
 }
 
@@ -1384,6 +1507,7 @@ int az_chess_engine_set_weights(az_chess_engine* e, const az_tensor* tensors, in
 
 int az_chess_forward(az_chess_engine* e, const float* x, int n, float* probs, float* values) {
   if (!e || n < 0 || (n && (!x || !probs || !values))) return az::fail_abi(AZ_E_INVALID, "bad arguments");
+  if (e->cfg.evaluator != AZ_EVAL_NETWORK) return az::fail_abi(AZ_E_STATE, "engine has no network evaluator");
   if (!e->net.ready) return az::fail_abi(AZ_E_STATE, "az_chess_engine_set_weights was not called");
   AZ_HIP(hipSetDevice(e->device));
   const int chunk = e->g.slots;
@@ -1411,6 +1535,7 @@ int az_chess_selfplay_begin(az_chess_engine* e, int64_t first_game, int64_t n_ga
   if (e->cfg.evaluator == AZ_EVAL_NETWORK && !e->net.ready)
     return az::fail_abi(AZ_E_STATE, "network evaluator selected but az_chess_engine_set_weights was not called");
   AZ_HIP(hipSetDevice(e->device));
+  e->broken = false;  // every slot starts a fresh game
   for (CLane* L : e->lanes) L->pending_expand = false;  // (a search an error interrupted)
   int rc;
   if ((rc = sync_lanes(e))) return rc;
@@ -1463,8 +1588,9 @@ int az_chess_stats(az_chess_engine* e, az_stats* st) {
 int az_chess_selfplay_step(az_chess_engine* e, int n_moves, az_stats* st) {
   if (!e || n_moves < 0) return az::fail_abi(AZ_E_INVALID, "bad arguments");
   if (!e->smp.done_count) return az::fail_abi(AZ_E_STATE, "az_chess_selfplay_begin was not called");
-  AZ_HIP(hipSetDevice(e->device));
   int rc;
+  if ((rc = ready_to_search(e))) return rc;
+  AZ_HIP(hipSetDevice(e->device));
   for (int mv = 0; mv < n_moves; ++mv) {
     const int64_t m = e->clock.issued++;
     // lanes interleaved per simulation so every stream always has work queued
@@ -1617,6 +1743,7 @@ int az_chess_tree_reset(az_chess_engine* e, int n, const int32_t* slots, const a
   tree_reset_kernel<<<(n + 63) / 64, 64, 0, e->stream>>>(e->g, e->t, n, e->tree_slots, e->tree_roots);
   AZ_HIP(hipGetLastError());
   AZ_HIP(hipStreamSynchronize(e->stream));
+  e->broken = false;
   return 0;
 }
 
@@ -1634,10 +1761,9 @@ int az_chess_tree_release(az_chess_engine* e, int n, const int32_t* slots) {
 
 int az_chess_tree_search(az_chess_engine* e, int n_sims) {
   if (!e || n_sims < 0) return az::fail_abi(AZ_E_INVALID, "bad arguments");
-  if (e->cfg.evaluator == AZ_EVAL_NETWORK && !e->net.ready)
-    return az::fail_abi(AZ_E_STATE, "network evaluator selected but az_chess_engine_set_weights was not called");
-  AZ_HIP(hipSetDevice(e->device));
   int rc;
+  if ((rc = ready_to_search(e))) return rc;
+  AZ_HIP(hipSetDevice(e->device));
   for (int s = 0; s < n_sims; ++s)
     for (CLane* L : e->lanes)
       if ((rc = simulate(e, *L))) return rc;
@@ -1650,6 +1776,7 @@ int az_chess_tree_search(az_chess_engine* e, int n_sims) {
 int az_chess_tree_play(az_chess_engine* e, const double* uniforms, int greedy, int deterministic, int32_t* moves,
                        int32_t* status, int32_t* policy_n, int16_t* policy_actions, double* policy_probs) {
   if (!e || (!deterministic && !uniforms)) return az::fail_abi(AZ_E_INVALID, "bad arguments");
+  if (e->broken) return ready_to_search(e);
   AZ_HIP(hipSetDevice(e->device));
   int rc;
   if ((rc = sync_lanes(e)) || (rc = tree_buffers(e))) return rc;

@@ -466,6 +466,29 @@ def _same_position(a, b):
     return bytes(np.asarray(a).tobytes()) == bytes(np.asarray(b).tobytes())
 
 
+def full_states(boards) -> np.ndarray:
+    """[b.full_state for b in boards] as one (n, 8, 8, 118) float64 array,
+    encoded by one batched kernels.encode (the arena's raw-policy batch).  A
+    board whose history does not end in its own position (see full_state)
+    takes the per-board path."""
+    n = len(boards)
+    hist = np.zeros((n, K.HISTORY), K.POS_DTYPE)
+    valid = np.zeros((n, K.HISTORY), np.uint8)
+    odd = []
+    for i, b in enumerate(boards):
+        for j, e in enumerate(list(b.state_history.entries)[-K.HISTORY:]):
+            if e is not None:
+                hist[i, j], valid[i, j] = e, 1
+        last = hist[i, K.HISTORY - 1].copy()
+        last["repetition"] = 0
+        if valid[i, -1] == 0 or not _same_position(last, b._pos):
+            odd.append(i)
+    out = K.encode(hist, valid).astype(np.float64) if n else np.zeros((0, 8, 8, K.PLANES))
+    for i in odd:
+        out[i] = boards[i].full_state
+    return out
+
+
 class _History:
     """state_history: the reference keeps a deque(maxlen=history_size) of
     state arrays; here the positions, encoded on demand (GPU).  Iterating

@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_lib", "lib
 
 EVAL_NETWORK = 0
 EVAL_SYNTHETIC = 1
-EVAL_HOST = 2  # include/az.h AZ_EVAL_HOST: a Python callable (Engine.set_host_evaluator)
+EVAL_HOST = 2  # include/az.h AZ_EVAL_HOST: a Python callable (Engine / ChessEngine.set_host_evaluator)
 CONV_F16X2 = 0  # include/az.h AZ_CONV_F16X2 (default)
 CONV_DIRECT = 1
 CONV_F16X2_LAYERS = 2  # AZ_CONV_F16X2_LAYERS: the same arithmetic one layer per launch (A/B runs)
@@ -105,6 +105,7 @@ EXPORTED = (
     # include/az_chess.h
     "az_chess_all_moves", "az_chess_legal", "az_chess_encode", "az_chess_play", "az_chess_perft",
     "az_chess_engine_create", "az_chess_engine_destroy", "az_chess_engine_set_weights",
+    "az_chess_engine_set_evaluator",
     "az_chess_forward", "az_chess_selfplay_begin", "az_chess_selfplay_step", "az_chess_selfplay_run",
     "az_chess_selfplay_results", "az_chess_selfplay_drain", "az_chess_stats", "az_chess_timer_enable",
     "az_chess_tree_reset",
@@ -179,6 +180,7 @@ def load_library():
                                                   ctypes.POINTER(P)]),
         "az_chess_engine_destroy": (ctypes.c_int, [P]),
         "az_chess_engine_set_weights": (ctypes.c_int, [P, ctypes.POINTER(Tensor), ctypes.c_int]),
+        "az_chess_engine_set_evaluator": (ctypes.c_int, [P, EVAL_FN, P]),
         "az_chess_forward": (ctypes.c_int, [P, P, ctypes.c_int, P, P]),
         "az_chess_selfplay_begin": (ctypes.c_int, [P, I64, I64, ctypes.c_uint32]),
         "az_chess_selfplay_step": (ctypes.c_int, [P, ctypes.c_int, ctypes.POINTER(Stats)]),
@@ -583,7 +585,8 @@ class Trainer:
 class ChessEngine:
     """libaz chess self-play engine (include/az_chess.h): `slots` concurrent
     chess games on one device, MCTS with the policy/value network on the
-    (8, 8, 118) Board.full_state planes and the 1880-move action space."""
+    (8, 8, 118) Board.full_state planes and the 1880-move action space -- or,
+    with evaluator=EVAL_HOST, with any Python callable (set_host_evaluator)."""
 
     ACTIONS = 1880
     MAX_MOVES = 256
@@ -603,6 +606,8 @@ class ChessEngine:
         handle = ctypes.c_void_p()
         _check(L.az_chess_engine_create(int(device), ctypes.byref(cfg), ctypes.byref(handle)))
         self._h, self._L, self._n_games = handle, L, 0
+        self._host_fn = None     # the EVAL_FN object (kept alive while the engine may call it)
+        self._host_error = None  # an exception the host evaluator raised inside a search
 
     def close(self):
         if getattr(self, "_h", None):
@@ -618,6 +623,45 @@ class ChessEngine:
     def set_weights(self, named):
         arr, n, _keep = tensor_array(named)
         _check(self._L.az_chess_engine_set_weights(self._h, arr, n))
+
+    def set_host_evaluator(self, fn):
+        """EVAL_HOST engines: fn(x) with x [n, 8, 8, 118] float32 (Board.full_state
+        of each leaf, every plane) returns (probs [n, 1880], values [n] or
+        [n, 1]) -- the reference's self.model(x) call (mcts.py:130-137), here
+        once per simulation and lane over every leaf that needs an evaluation
+        (az_chess_engine_set_evaluator).  Outputs may be numpy arrays or torch
+        / TF tensors; a wrong shape raises ValueError.  An exception inside fn
+        ends the search and is re-raised by the call that ran it."""
+        A = self.ACTIONS
+
+        def cb(_user, xp, n, pp, vp):
+            try:
+                x = np.ctypeslib.as_array(xp, shape=(n, 8, 8, 118)).copy()
+                p, v = fn(x)
+                p = _as_numpy(p).astype(np.float32, copy=False)
+                v = _as_numpy(v).astype(np.float32, copy=False)
+                if p.shape != (n, A):
+                    raise ValueError(f"the host evaluator returned probs of shape {p.shape}, expected {(n, A)}")
+                if v.shape not in ((n,), (n, 1)):
+                    raise ValueError(f"the host evaluator returned values of shape {v.shape}, "
+                                     f"expected {(n,)} or {(n, 1)}")
+                np.ctypeslib.as_array(pp, shape=(n, A))[:] = p
+                np.ctypeslib.as_array(vp, shape=(n,))[:] = v.reshape(n)
+                return 0
+            except BaseException as ex:  # noqa: BLE001 - handed back to the caller below
+                self._host_error = ex
+                return 1
+
+        host_fn = EVAL_FN(cb)
+        _check(self._L.az_chess_engine_set_evaluator(self._h, host_fn, None))
+        self._host_fn = host_fn
+
+    def _search_call(self, rc):
+        """_check for calls that can run the host evaluator: its exception first."""
+        if self._host_error is not None:
+            ex, self._host_error = self._host_error, None
+            raise ex
+        _check(rc)
 
     def forward(self, x):
         x = np.ascontiguousarray(x, np.float32).reshape(-1, 8, 8, 118)
@@ -636,10 +680,10 @@ class ChessEngine:
         stats) and selfplay_drain returns the games of the newest move whose
         snapshot is complete (az_chess_selfplay_step with st = NULL, ABI 10)."""
         if not sync:
-            _check(self._L.az_chess_selfplay_step(self._h, int(n_moves), None))
+            self._search_call(self._L.az_chess_selfplay_step(self._h, int(n_moves), None))
             return None
         st = Stats()
-        _check(self._L.az_chess_selfplay_step(self._h, int(n_moves), ctypes.byref(st)))
+        self._search_call(self._L.az_chess_selfplay_step(self._h, int(n_moves), ctypes.byref(st)))
         return st.as_dict()
 
     def selfplay_drain(self, max_games=None, chunk=64):
@@ -672,8 +716,8 @@ class ChessEngine:
 
     def selfplay_run(self, first_game, n_games, base_seed):
         st = Stats()
-        _check(self._L.az_chess_selfplay_run(self._h, int(first_game), int(n_games),
-                                             int(base_seed) & 0xFFFFFFFF, ctypes.byref(st)))
+        self._search_call(self._L.az_chess_selfplay_run(self._h, int(first_game), int(n_games),
+                                                        int(base_seed) & 0xFFFFFFFF, ctypes.byref(st)))
         self._n_games = int(n_games)
         return st.as_dict()
 
@@ -714,7 +758,7 @@ class ChessEngine:
         _check(self._L.az_chess_tree_release(self._h, len(slots), _ptr(slots)))
 
     def tree_search(self, n_sims):
-        _check(self._L.az_chess_tree_search(self._h, int(n_sims)))
+        self._search_call(self._L.az_chess_tree_search(self._h, int(n_sims)))
 
     def tree_play(self, uniforms=None, greedy=False, deterministic=False):
         """-> moves [S] (move codes, -1 idle), status [S] (AZ_CHESS_* of the new

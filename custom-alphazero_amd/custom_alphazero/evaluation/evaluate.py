@@ -14,13 +14,35 @@
   search's root-noise vectors, then play's draw, from the game's stream.
 The exact-solver scoring path needs the refused c4solver binary (SURVEY.md
 section 8c) and raises NotImplementedError.
+
+The game is ConfigGeneral.game, read at call time (evaluate.py:16-26 picks
+Board, Move and get_all_possible_moves by it): "connect_n" as above, "chess"
+with chess.board.Board and chess.utils.get_all_possible_moves.  Rules of a
+chess arena game:
+* decisive means bool(board.get_result()) -- chess get_result takes no
+  keep_same_player; on the canonical board a checkmate is a win for the side
+  that just moved, and the last mover is credited; everything else is a draw;
+* a game that reaches ConfigSelfPlay.chess_max_plies plies without an outcome
+  is a draw (the engine's own addition: the reference has no cap);
+* greedy is the reference's expression on the game's own board,
+  fullmove_number > ConfigMCTS.index_move_greedy;
+* the models alternate as in evaluate.py:39, 61-62, 75-83;
+* a model is a PolicyValueModel (a network engine) or, under MCTS, any other
+  callable model(x) -> (probabilities, value) (a host-evaluator engine);
+* Dirichlet root noise stays refused (check_mcts_config("chess")), and `trace`
+  collects the final boards' az_chess_pos records.
+The batched chess arena searches each ply with az_chess_tree_release /
+_reset / _search / _play; its raw-policy mode encodes every live board in one
+batched kernels.encode.  deterministic=True gives the sequential loop's
+per-game results and final positions; stochastic play draws from each game's
+own stream, one draw per move as Connect-N.
 """
 from typing import List, Optional, Tuple
 
 import numpy as np
 
 from custom_alphazero import engine as az
-from custom_alphazero.config import (ConfigConnectN, ConfigMCTS, ConfigModel, ConfigSelfPlay,
+from custom_alphazero.config import (ConfigConnectN, ConfigGeneral, ConfigMCTS, ConfigModel, ConfigSelfPlay,
                                      ConfigServing, check_mcts_config)
 from custom_alphazero.connect_n.board import Board
 from custom_alphazero.connect_n.move import Move
@@ -28,6 +50,76 @@ from custom_alphazero.mcts.mcts import MCTS, root_noise_rows
 from custom_alphazero.mcts.utils import normalize_probabilities
 
 get_all_possible_moves = Board.get_all_possible_moves
+
+
+def _game():
+    """(Board, get_all_possible_moves, is chess) of ConfigGeneral.game, resolved
+    per call (evaluate.py:16-26 resolves it at import)."""
+    if ConfigGeneral.game == "connect_n":
+        return Board, get_all_possible_moves, False
+    if ConfigGeneral.game == "chess":
+        from custom_alphazero.chess.board import Board as ChessBoard
+        from custom_alphazero.chess.utils import get_all_possible_moves as chess_moves
+        return ChessBoard, chess_moves, True
+    raise NotImplementedError(f"no arena for ConfigGeneral.game = {ConfigGeneral.game!r}")
+
+
+def _chess_legal_policy(probabilities, board, all_possible_moves):
+    return normalize_probabilities(probabilities[board.legal_moves_mask(all_possible_moves)])
+
+
+def _chess_pick(board, legal, deterministic: bool, rng):
+    """The raw-policy move of a chess board: argmax, or rng.choice's one draw over the move indices."""
+    moves = board.moves
+    if deterministic:
+        return moves[int(np.argmax(legal))]
+    return moves[int(rng.choice(len(moves), 1, p=legal).item())]
+
+
+def _single_chess_game(current_model, previous_model, game_index: int, all_possible_moves,
+                       evaluate_with_mcts: bool, deterministic: bool, rng, trace):
+    """_single_game_evaluation's loop (evaluate.py:29-98) on a chess board."""
+    ChessBoard = _game()[0]
+    cap = max(int(ConfigSelfPlay.chess_max_plies), 1)
+    model = current_model if game_index % 2 == 0 else previous_model
+    plies = 0
+    if not evaluate_with_mcts:
+        board = ChessBoard()
+        while not board.is_game_over() and plies < cap:
+            probabilities, _ = model(np.expand_dims(board.full_state, axis=0))
+            legal = _chess_legal_policy(az._as_numpy(probabilities).ravel(), board, all_possible_moves)
+            board.play(_chess_pick(board, legal, deterministic, rng), keep_same_player=True)
+            plies += 1
+            if not board.is_game_over():
+                model = previous_model if model is current_model else current_model
+    else:
+        mcts = MCTS(board=ChessBoard(), all_possible_moves=all_possible_moves, concurrency=False,
+                    model=model, plays_inferences={})
+        while not mcts.board.is_game_over() and plies < cap:
+            greedy = mcts.board.fullmove_number > ConfigMCTS.index_move_greedy
+            mcts.search(ConfigSelfPlay.mcts_iterations)
+            if rng is not np.random and not deterministic:
+                # play draws its move from np.random: route this game's stream through it
+                state = np.random.get_state()
+                np.random.set_state(rng.get_state())
+                try:
+                    mcts.play(greedy, deterministic=deterministic)
+                finally:
+                    rng.set_state(np.random.get_state())
+                    np.random.set_state(state)
+            else:
+                mcts.play(greedy, deterministic=deterministic)
+            plies += 1
+            if not mcts.board.is_game_over() and plies < cap:
+                model = previous_model if mcts.model is current_model else current_model
+                mcts = MCTS(board=mcts.board, all_possible_moves=all_possible_moves,
+                            concurrency=False, model=model, plays_inferences={})
+        board = mcts.board
+    if trace is not None:
+        trace.append(board._pos.copy())
+    if board.get_result():  # None (the cap) and 0 (a draw) are not decisive
+        return (1 if current_model is model else -1), []
+    return 0, []
 
 
 def _policy_move(model, board: Board, all_possible_moves: List[Move], deterministic: bool, rng):
@@ -49,6 +141,9 @@ def _single_game_evaluation(current_model, previous_model, game_index: int,
     if evaluate_with_solver:
         raise NotImplementedError("solver scoring needs the c4solver binary (not run here)")
     rng = np.random if rng is None else rng
+    if _game()[2]:
+        return _single_chess_game(current_model, previous_model, game_index, all_possible_moves,
+                                  evaluate_with_mcts, deterministic, rng, trace)
     model = current_model if game_index % 2 == 0 else previous_model
     if not evaluate_with_mcts:
         board = Board()
@@ -102,7 +197,7 @@ def evaluate_two_models(model, other_model, evaluate_with_mcts: bool = False,
     """evaluate.py:101-134: (score of `model`, solver score or None)."""
     if evaluate_with_solver:
         raise NotImplementedError("solver scoring needs the c4solver binary (not run here)")
-    all_possible_moves = get_all_possible_moves()
+    all_possible_moves = _game()[1]()
     results = [_single_game_evaluation(model, other_model, g, all_possible_moves,
                                        evaluate_with_mcts, False, deterministic)[0]
                for g in range(ConfigServing.evaluation_games_number)]
@@ -125,12 +220,102 @@ def _arena_engine(model, n_slots: int) -> az.Engine:
     return eng
 
 
+def _chess_arena_engine(model, n_slots: int) -> az.ChessEngine:
+    """One chess engine of n_slots trees for `model`: a network engine for a
+    PolicyValueModel, a host-evaluator engine for any other callable."""
+    check_mcts_config("chess")
+    sims = max(ConfigSelfPlay.mcts_iterations, 1)
+    if model is not None and hasattr(model, "engine_weights"):
+        evaluator = az.EVAL_NETWORK
+    elif callable(model):
+        evaluator = az.EVAL_HOST
+    else:
+        raise TypeError("the chess arena needs PolicyValueModels or callables model(x) -> (probabilities, value)")
+    eng = az.ChessEngine(mcts_iterations=sims, slots=n_slots, evaluator=evaluator,
+                         max_plies=max(ConfigSelfPlay.chess_max_plies, 1),
+                         index_move_greedy=ConfigMCTS.index_move_greedy,
+                         exploration_constant=ConfigMCTS.exploration_constant,
+                         filters=ConfigModel.filters, depth=ConfigModel.depth,
+                         value_hidden=ConfigModel.value_hidden, bn_epsilon=ConfigModel.bn_epsilon,
+                         arena_edges=160 * sims + 4096, lanes=1)
+    if evaluator == az.EVAL_NETWORK:
+        eng.set_weights(model.engine_weights())
+    else:
+        eng.set_host_evaluator(model)
+    return eng
+
+
+def _chess_arena_batched(model, other_model, n: int, evaluate_with_mcts: bool, deterministic: bool,
+                         seed: int, trace: Optional[list]):
+    from custom_alphazero.chess.board import full_states
+    from custom_alphazero.chess.move import Move as ChessMove
+    ChessBoard, chess_moves, _ = _game()
+    all_moves = chess_moves()
+    cap = max(int(ConfigSelfPlay.chess_max_plies), 1)
+    boards = [ChessBoard() for _ in range(n)]
+    side = np.array([g % 2 for g in range(n)])  # 0: `model` to move, 1: `other_model`
+    rngs = [np.random.RandomState((seed + g) % 2 ** 32) for g in range(n)]
+    models = (model, other_model)
+    engines = [_chess_arena_engine(m, n) for m in models] if evaluate_with_mcts else None
+    active = [set(), set()]
+    last_side = np.zeros(n, np.int64)
+    try:
+        for _ply in range(cap):
+            live = [g for g in range(n) if not boards[g].is_game_over()]
+            if not live:
+                break
+            for s in (0, 1):
+                idx = [g for g in live if side[g] == s]
+                if not idx:
+                    continue
+                if not evaluate_with_mcts:
+                    x = full_states([boards[g] for g in idx])  # one batched encode
+                    probs = az._as_numpy(models[s](x)[0])
+                    for k, g in enumerate(idx):
+                        legal = _chess_legal_policy(probs[k], boards[g], all_moves)
+                        boards[g].play(_chess_pick(boards[g], legal, deterministic, rngs[g]),
+                                       keep_same_player=True)
+                else:
+                    eng = engines[s]
+                    stale = sorted(active[s] - set(idx))
+                    if stale:
+                        eng.tree_release(stale)
+                    eng.tree_reset(idx, np.stack([boards[g]._pos for g in idx]))
+                    active[s] = set(idx)
+                    eng.tree_search(ConfigSelfPlay.mcts_iterations)
+                    u = None
+                    if not deterministic:
+                        u = np.zeros(n)
+                        for g in idx:
+                            u[g] = rngs[g].random_sample()  # np.random.choice's one draw (mcts.py:201)
+                    # the games move in lockstep from one start position: one greedy flag per ply
+                    greedy = {boards[g].fullmove_number > ConfigMCTS.index_move_greedy for g in idx}
+                    if len(greedy) != 1:
+                        raise RuntimeError("the live games disagree on fullmove_number")
+                    out = eng.tree_play(u, greedy=greedy.pop(), deterministic=deterministic)
+                    for g in idx:
+                        boards[g].play(ChessMove.from_code(int(out["moves"][g])), keep_same_player=True)
+                last_side[idx] = s
+            side = 1 - side
+    finally:
+        for eng in engines or ():
+            eng.close()
+    results = []
+    for g in range(n):
+        if trace is not None:
+            trace.append(boards[g]._pos.copy())
+        results.append(0 if not boards[g].get_result() else (1 if last_side[g] == 0 else -1))
+    return _score(results), results
+
+
 def evaluate_two_models_batched(model, other_model, n_games: Optional[int] = None,
                                 evaluate_with_mcts: bool = False, deterministic: bool = True,
                                 seed: int = 0, trace: Optional[list] = None):
     """All games at once.  Returns (score of `model`, per-game results);
-    `trace` collects the final boards' arrays in game order."""
+    `trace` collects the final boards' arrays (chess: az_chess_pos records) in game order."""
     n = int(n_games or ConfigServing.evaluation_games_number)
+    if _game()[2]:
+        return _chess_arena_batched(model, other_model, n, evaluate_with_mcts, deterministic, seed, trace)
     all_moves = get_all_possible_moves()
     A = len(all_moves)
     boards = [Board() for _ in range(n)]

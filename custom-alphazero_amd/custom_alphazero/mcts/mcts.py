@@ -245,12 +245,16 @@ def _chess_engine_for(model):
         evaluator = az.EVAL_SYNTHETIC
     elif model is not None and hasattr(model, "engine_weights"):
         evaluator = az.EVAL_NETWORK
+    elif callable(model):
+        # any other model is called as the reference calls it (mcts.py:130-137):
+        # model(x) -> (probabilities, value), x the (n, 8, 8, 118) full_state planes
+        # of a simulation's leaves (az_chess_engine_set_evaluator)
+        evaluator = az.EVAL_HOST
     else:
-        # the chess engine has no host-evaluator seam (az_chess_config.evaluator
-        # is AZ_EVAL_NETWORK or AZ_EVAL_SYNTHETIC): a plain callable model is refused
         raise TypeError(
-            "chess MCTS on the MI355X engine needs a custom_alphazero PolicyValueModel or a "
-            "SyntheticEvaluator (the chess engine has no host-evaluator seam for other callables)")
+            "chess MCTS on the MI355X engine needs a model (a custom_alphazero PolicyValueModel, "
+            "SyntheticEvaluator or any callable model(x) -> (probabilities, value)); HTTP "
+            "inference and the exact solver are not on the device path")
     sims = max(SP.mcts_iterations, 1)
     max_plies = max(SP.chess_max_plies, 1)
     # a tree holds at most the visits of its root: sims per search plus the
@@ -263,12 +267,14 @@ def _chess_engine_for(model):
                          arena_edges=160 * sims + 4096)
     if evaluator == az.EVAL_NETWORK:
         eng.set_weights(model.engine_weights())
+    elif evaluator == az.EVAL_HOST:
+        eng.set_host_evaluator(model)
     return eng
 
 
 class ChessMCTS(MCTS):
     """MCTS (mcts.py:86-222) with a chess board: search, expansion (network
-    on Board.full_state, priors zipped with python-chess's move order),
+    -- or any callable model -- on Board.full_state, priors zipped with python-chess's move order),
     backup and play run on the device (az_chess_tree_*).  The root is
     evaluated with the history of a deepcopied board, [0 x 7, start-position
     state] (python-chess copy() re-runs the reference subclass's __init__),

@@ -137,15 +137,33 @@ def _batched_engine(model, n_slots, sims=None):
 _CHESS_ENGINES = {}
 
 
+def _chess_evaluator(model):
+    """The three-way choice of mcts._chess_engine_for: the synthetic marker,
+    a model with engine_weights (the network), or any other callable (the
+    host seam, az_chess_engine_set_evaluator)."""
+    if isinstance(model, SyntheticEvaluator):
+        return az.EVAL_SYNTHETIC
+    if model is not None and hasattr(model, "engine_weights"):
+        return az.EVAL_NETWORK
+    if callable(model):
+        return az.EVAL_HOST
+    raise TypeError("chess self-play needs a model (a custom_alphazero PolicyValueModel, SyntheticEvaluator "
+                    "or any callable model(x) -> (probabilities, value))")
+
+
 def _chess_engine(model, n_slots, sims):
     check_mcts_config("chess")
-    synthetic = isinstance(model, SyntheticEvaluator)
+    evaluator = _chess_evaluator(model)
+    synthetic = evaluator == az.EVAL_SYNTHETIC
+    # a callable is part of the key by identity: another callable gets another engine
     key = (sims, n_slots, synthetic, ConfigMCTS.index_move_greedy, ConfigMCTS.exploration_constant,
-           ConfigModel.depth, ConfigSelfPlay.chess_max_plies, ConfigSelfPlay.chess_cache_log2)
+           ConfigModel.depth, ConfigSelfPlay.chess_max_plies, ConfigSelfPlay.chess_cache_log2,
+           id(model) if evaluator == az.EVAL_HOST else None)
     eng = _CHESS_ENGINES.get(key)
+    if eng is not None and evaluator == az.EVAL_HOST and eng.host_model is not model:
+        eng = None  # (an id reused by a new object)
     if eng is None:
-        eng = az.ChessEngine(sims, slots=n_slots,
-                             evaluator=az.EVAL_SYNTHETIC if synthetic else az.EVAL_NETWORK,
+        eng = az.ChessEngine(sims, slots=n_slots, evaluator=evaluator,
                              max_plies=ConfigSelfPlay.chess_max_plies,
                              index_move_greedy=ConfigMCTS.index_move_greedy,
                              exploration_constant=ConfigMCTS.exploration_constant,
@@ -153,9 +171,13 @@ def _chess_engine(model, n_slots, sims):
                              value_hidden=ConfigModel.value_hidden, bn_epsilon=ConfigModel.bn_epsilon,
                              cache_log2=ConfigSelfPlay.chess_cache_log2)
         eng.weights_key = None
+        eng.host_model = None
+        if evaluator == az.EVAL_HOST:
+            eng.set_host_evaluator(model)
+            eng.host_model = model  # (keeps the callable, and so its id, alive with the engine)
         _CHESS_ENGINES.clear()
         _CHESS_ENGINES[key] = eng
-    if not synthetic:
+    if evaluator == az.EVAL_NETWORK:
         wkey = model.content_hash if hasattr(model, "content_hash") else (id(model), getattr(model, "_version", None))
         if eng.weights_key != wkey:
             eng.set_weights(model.engine_weights())
@@ -164,7 +186,9 @@ def _chess_engine(model, n_slots, sims):
 
 
 def play_chess(model, n_games: int, base_seed: int, first_game: int = 0, sims: Optional[int] = None):
-    """Batched chess self-play (BASELINE configs[4]).  Returns (states
+    """Batched chess self-play (BASELINE configs[4]); `model` is a
+    PolicyValueModel, a SyntheticEvaluator or any callable model(x) ->
+    (probabilities, value) on (n, 8, 8, 118) states.  Returns (states
     [M,8,8,118] f32 -- Board.full_state of each MCTS.play parent board, exact
     in f32 --, policies [M,1880] f64, rewards [M], records), in game order."""
     from custom_alphazero.chess import kernels as K

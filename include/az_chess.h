@@ -103,7 +103,8 @@ typedef struct az_chess_config {
     int32_t index_move_greedy;    /* greedy once fullmove_number >= this (self_play.py:62) */
     double exploration_constant;  /* ConfigMCTS.exploration_constant */
     int32_t slots;                /* concurrent games on this device */
-    int32_t evaluator;            /* AZ_EVAL_NETWORK or AZ_EVAL_SYNTHETIC */
+    int32_t evaluator;            /* AZ_EVAL_NETWORK, AZ_EVAL_SYNTHETIC or AZ_EVAL_HOST (a host
+                                     callback: az_chess_engine_set_evaluator) */
     int32_t filters, depth, value_hidden;  /* ConfigModel (filters must be 128) */
     int32_t max_plies;            /* addition: games stop (as draws) after this many plies;
                                      the reference has no cap (0 = 512) */
@@ -126,7 +127,11 @@ typedef struct az_chess_config {
  * a search at all (chess/board.py:178's get_result signature vs mcts.py:179),
  * so there is no noisy chess behaviour to match; the Python layer refuses
  * the flag for chess (config.check_mcts_config("chess")) instead of
- * ignoring it.  Connect-N has it in self-play and in the tree API (az.h). */
+ * ignoring it.  Connect-N has it in self-play and in the tree API (az.h).
+ * Evaluators: the network (AZ_EVAL_NETWORK), the oracle's synthetic function
+ * (AZ_EVAL_SYNTHETIC) or a host callback (AZ_EVAL_HOST,
+ * az_chess_engine_set_evaluator): self-play, the tree API and, in Python,
+ * MCTS on a chess Board and the two-model arena run with any of them. */
 
 /* Termination of a finished self-play game: AZ_CHESS_* above, or this */
 #define AZ_CHESS_MAX_PLIES 5
@@ -134,8 +139,34 @@ typedef struct az_chess_config {
 int az_chess_engine_create(int device, const az_chess_config* cfg, az_chess_engine** out);
 int az_chess_engine_destroy(az_chess_engine* eng);
 /* PolicyValueModel weights for input_dim (8, 8, 118), action_space 1880
- * (model/tensorflow/model.py:152-188; names of custom_alphazero/model/weights.py) */
+ * (model/tensorflow/model.py:152-188; names of custom_alphazero/model/weights.py);
+ * AZ_EVAL_NETWORK engines only */
 int az_chess_engine_set_weights(az_chess_engine* eng, const az_tensor* tensors, int n);
+/* AZ_EVAL_HOST (added after ABI 10 without a version bump: the change only
+ * adds): the evaluator of an engine created with AZ_EVAL_HOST, az.h's
+ * az_eval_fn -- the reference's duck-typed self.model(x) seam
+ * (mcts/mcts.py:130-137) for chess boards.  AZ_E_STATE on an engine created
+ * with another evaluator.  The search calls it once per simulation and lane
+ * with the leaves that need an evaluation -- after the transposition cache
+ * and, where the cache is on, after the per-simulation sharing of identical
+ * leaves -- as x [n][8][8][118] f32, contiguous: exactly Board.full_state of
+ * each leaf, all 118 planes (the history planes 0-83 the self-play tower
+ * skips included), in the history form of the tree API below: [0 x 7, start]
+ * for a root set by reset or a game's first board, [0 x 6, start, board]
+ * otherwise.  It writes the model's raw outputs probs [n][1880] (before the
+ * legal-move mask and renormalisation, mcts.py:147-150) and values [n], and
+ * returns 0; n <= 0 makes no call.  Host buffers, valid during the call.  A
+ * nonzero return fails the search with AZ_E_CALLBACK, and the simulation it
+ * interrupted leaves the trees incomplete: az_chess_selfplay_step,
+ * az_chess_selfplay_run's steps, az_chess_tree_search and az_chess_tree_play
+ * then fail with AZ_E_STATE until az_chess_selfplay_begin or
+ * az_chess_tree_reset.  Searching before a callback is set is AZ_E_STATE.
+ * The outputs must be a deterministic function of x (the cache relies on it,
+ * as the reference's plays_inferences dict does); results are identical with
+ * the cache on or off.  az_chess_forward and az_chess_engine_set_weights on
+ * such an engine answer AZ_E_STATE.  Every simulation waits for its callback,
+ * so az_chess_selfplay_step with st = NULL is effectively synchronous here. */
+int az_chess_engine_set_evaluator(az_chess_engine* eng, az_eval_fn fn, void* user);
 /* PolicyValueModel.__call__ on chess states: x [n][8][8][118] f32 (Board.full_state)
  * -> probs [n][1880] f32, values [n] f32 */
 int az_chess_forward(az_chess_engine* eng, const float* x, int n, float* probs, float* values);
