@@ -7,7 +7,9 @@
 // length, so:
 //   select   one wave per slot: PUCT over the node's edges (4 per lane),
 //            ΣN and first-max argmax by wave shuffles, the position replayed
-//            along the path with push + mirror (no boards stored per node)
+//            along the path with push + mirror (no boards stored per node);
+//            with Dirichlet root noise on, the root's vector drawn by the
+//            wave (az_dirichlet_wave.h) or taken from the caller's rows
 //   leaf     one wave per slot: legal moves (one square per lane) + outcome of
 //            the leaf; terminal leaves back up get_result's value, the rest
 //            join the eval queue
@@ -25,12 +27,15 @@
 #include <math.h>
 #include <string.h>
 
+#include <cmath>
+
 #include <algorithm>
 #include <string>
 #include <vector>
 
 #include "../../include/az_chess.h"
 #include "az_chess.h"
+#include "az_dirichlet_wave.h"
 #include "az_host.h"
 #include "az_nn.h"
 #include "az_tree.h"
@@ -45,6 +50,9 @@ using az::Edge;
 struct CCfg {
   int slots, sims, greedy_ply, half_cap, max_depth, max_plies, pow_len, evaluator;
   double c_puct;
+  // Dirichlet root noise (ConfigMCTS.enable_dirichlet_noise, mcts.py:70-85, 113-116)
+  int noise;
+  double noise_alpha, noise_ratio;
 };
 
 struct CTree {
@@ -52,6 +60,7 @@ struct CTree {
   az_chess_pos* root;      // [slots]
   int32_t* root_first;     // [slots]
   int32_t* root_n;         // [slots]
+  int32_t* root_f64;       // [slots] root noise: the root's priors are the float64 uniform form (kChildF64)
   int32_t* half;           // [slots] arena half holding the live tree
   int32_t* top;            // [slots] edges used in that half
   int32_t* ply;            // [slots]
@@ -91,9 +100,23 @@ struct CTree {
   int32_t* dup_count;      // this simulation's (the lane's counts block, alternating)
   int32_t* next_dup;       // the next simulation's (zeroed by this select launch)
   uint32_t* sel_done;      // [1] select blocks finished (the last resolves the duplicates)
+  // tree API root noise drawn by the host (az_chess_tree_search_noise): slot
+  // s's r-th root selection of the search mixes row noise_in[(s * noise_rows +
+  // r) * AZ_CHESS_MAX_MOVES + i] into edge i's prior; null: self-play draws on
+  // the device from the slot's MT19937
+  const double* noise_in;
+  int32_t* noise_cur;      // [slots] rows consumed
+  int32_t noise_rows;
 };
 
 constexpr int kQHit = -2, kQDup0 = -3;
+// Root noise mixes (1 - ratio) * priors in the priors' dtype: float32 after
+// normalize_probabilities' quotient, float64 after its zero-sum uniform branch
+// (mcts/utils.py:4-16).  The value cannot tell (1/n is exact in both when n is
+// a power of two), so engines with noise on carry the form: a node's in bit 14
+// of its parent edge's child_n (a count is <= 218), the root's in root_f64.
+// Engines without noise never set the bit, and their select reads child_n bare.
+constexpr int kChildF64 = 0x4000, kChildMask = 0x3fff;
 // transposition cache entry: key (position + history form), state word, payload
 struct ChessKey {
   az_chess_pos pos;  // 80 B
@@ -237,6 +260,7 @@ __device__ void slot_reset(const CCfg& g, const CTree& t, const CSamples& smp, i
   t.root[s] = a;
   t.root_first[s] = 0;
   t.root_n[s] = 0;
+  t.root_f64[s] = 0;
   t.half[s] = 0;
   t.top[s] = 0;
   t.ply[s] = 0;
@@ -277,6 +301,7 @@ __global__ void tree_reset_kernel(CCfg g, CTree t, int n, const int32_t* slots, 
   t.root[s] = roots[i];
   t.root_first[s] = 0;
   t.root_n[s] = 0;
+  t.root_f64[s] = 0;
   t.root_value[s] = 0.f;
   t.half[s] = 0;
   t.top[s] = 0;
@@ -544,15 +569,17 @@ __device__ void expand_body(const CCfg& g, const CTree& t, const ChessCache& c, 
     E[first + j] = e;
   }
   const int leaf_edge = depth > 64 ? path[depth - 1] : __shfl(pth, depth > 0 ? depth - 1 : 0, 64);
+  const int f64 = g.noise && sum == 0.0f;  // the priors' form, for root noise (kChildF64)
   if (lane == 0) {
     if (depth == 0) {
       t.root_first[s] = first;
       t.root_n[s] = n;
       t.root_value[s] = value;
+      if (g.noise) t.root_f64[s] = f64;
     } else {
       Edge& pe = E[leaf_edge];
       pe.child = first;
-      pe.child_n = (int16_t)n;
+      pe.child_n = (int16_t)(f64 ? n | kChildF64 : n);
       pe.child_value = value;
     }
   }
@@ -702,16 +729,119 @@ __device__ void dup_tail(const CTree& t, const ChessCache& c, int lane) {
 // outputs are still in probs / values), so a search is select,
 // (network, select) x (sims - 1), network, expand: one tree launch per
 // simulation on the lane's chain instead of two
-template <bool FUSED>
+//
+// NOISE (engines with Dirichlet root noise; the other instantiations carry
+// none of it): at the root, get_best_edge_with_noise (mcts.py:70-85) -- a
+// fresh np.random.dirichlet(alpha * ones(k)) per root selection, mixed into
+// the priors as numpy computes (1 - ratio) * priors + ratio * noise (the first
+// product in the priors' dtype, the rest float64), and np.argmax's order with
+// NaN above every number (a host evaluator can return anything).
+struct NoiseSmem {
+  double d[AZ_CHESS_MAX_MOVES];  // the gammas in component order, then the normalised vector
+  uint32_t cur[az::kMtWords];    // the slot's MT19937 state, read once per draw (every word fetch is an LDS read)
+  uint32_t next[az::kMtWords];   // the next state, staged until a round's used words cross into it
+  double invacc;
+  int row;
+};
+
+// np.argmax order: NaN above every number, then value, then the lower index
+__device__ __forceinline__ bool argmax_before(double v, int i, double bv, int bi) {
+  if (bv != bv) return v != v && i < bi;
+  if (v != v) return true;
+  return v > bv || (v == bv && i < bi);
+}
+
+// RandomState.dirichlet(alpha * ones(k)) on slot s's MT19937 stream by the
+// slot's wave into sm.d[0..k): az_dirichlet_wave.h's rounds of 64 attempts.
+// The word-major state is copied to LDS first -- ten independent loads per
+// lane and the position, one memory round trip; a round's words and the twist
+// then read LDS (fetched from memory, the twist's strided loads were a chain
+// of round trips) -- and a committed next state is stored back.  The stream
+// ends exactly where numpy's serial draw leaves it.  False: the round cap (a
+// defect; kErrDraw flagged).
+__device__ __forceinline__ bool dirichlet_wave(const CCfg& g, const CTree& t, int s, int lane, int k, NoiseSmem& sm) {
+  const size_t slots = (size_t)t.mt_stride;
+  uint32_t* m = t.mt + s;
+  const double shape = g.noise_alpha, inv = 1.0 / shape;
+  const int wpa = az::draw_words_per_attempt(shape);
+  auto old = [&](int i) { return sm.cur[i]; };
+  auto nw = [&](int i) { return sm.next[i]; };
+  for (int i = lane; i < kMtN; i += 64) sm.cur[i] = m[(size_t)i * slots];
+  int pos = (int)m[(size_t)kMtN * slots];  // wave-uniform, 0..624
+  __syncthreads();
+  int have = 0;
+  for (int round = 0; have < k; ++round) {  // every condition below is wave-uniform
+    if (round >= az::kDrawMaxRounds || pos > kMtN) {
+      if (lane == 0) flag(t, az::kErrDraw);
+      return false;
+    }
+    const bool staged = az::draw_round_needs_next(pos, wpa);
+    if (staged) {
+      for (int ph = 0; ph < 3; ++ph) {
+        for (int i = az::mt_phase_begin(ph) + lane; i < az::mt_phase_end(ph); i += 64)
+          sm.next[i] = az::mt_twist_word(i, old, nw);
+        __syncthreads();
+      }
+    }
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      if (q < wpa) {
+        const int i = pos + lane * wpa + q;  // < pos + 256 <= 624 + 256
+        w[q] = az::mt_temper(i < kMtN ? sm.cur[i] : sm.next[i - kMtN]);
+      }
+    }
+    double x;
+    const bool ok = az::gamma_attempt(w, shape, inv, &x);
+    const uint64_t accepted = __ballot(ok);
+    const int j = az::draw_component(accepted, lane, have);
+    if (ok && j < k) sm.d[j] = x;
+    const int used = az::draw_round_used(accepted, have, k);
+    bool commit;
+    pos = az::draw_round_advance(pos, used, wpa, &commit);
+    if (commit) {  // (every lane's word reads of this round are done: the ballot above)
+      for (int i = lane; i < kMtN; i += 64) {
+        const uint32_t v = sm.next[i];
+        sm.cur[i] = v;
+        m[(size_t)i * slots] = v;
+      }
+    }
+    have += __builtin_popcountll(accepted);
+    __syncthreads();
+  }
+  if (lane == 0) {
+    m[(size_t)kMtN * slots] = (uint32_t)pos;
+    double acc = 0.0;  // mtrand's loop: acc = acc + g_j, left to right
+    for (int j = 0; j < k; ++j) acc = acc + sm.d[j];
+    sm.invacc = 1 / acc;
+  }
+  __syncthreads();
+  const double invacc = sm.invacc;
+  for (int j = lane; j < k; j += 64) sm.d[j] = sm.d[j] * invacc;
+  __syncthreads();
+  return true;
+}
+
+template <bool FUSED, bool NOISE>
 __device__ __forceinline__ void select_slot(const CCfg& g, const CTree& t, const ChessCache& c,
                                             const float* __restrict__ probs, const float* __restrict__ values,
-                                            uint16_t* cand, ExpandSmem& esm) {
+                                            uint16_t* cand, ExpandSmem& esm, NoiseSmem* nsm) {
   const int s = blockIdx.x, lane = threadIdx.x;
   if (t.game_id[s] < 0) return;
   if constexpr (FUSED) {
     const int b = t.slot_q[s];  // wave-uniform
     if (b >= 0 || b == kQHit) {
-      expand_body(g, t, c, probs, values, b, s, lane, esm);
+      // NOISE: inlined by force here and at dup_tail below.  The larger kernel
+      // made the inliner leave one of them out of line, and a call takes the
+      // by-reference CCfg / CTree / ChessCache kernel arguments through scratch:
+      // every later field access of the descent became a scratch load.  The
+      // other instantiations keep the inliner's own choice, so their code is
+      // what it was.
+      if constexpr (NOISE) {
+        [[clang::always_inline]] expand_body(g, t, c, probs, values, b, s, lane, esm);
+      } else {
+        expand_body(g, t, c, probs, values, b, s, lane, esm);
+      }
       // the wave's edge and path stores complete before its descent reads them
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     }
@@ -741,23 +871,73 @@ __device__ __forceinline__ void select_slot(const CCfg& g, const CTree& t, const
     const double sq = t.powtab[sum];
     double best_v = -INFINITY;
     int best = 1 << 30;
-    for (int j = lane; j < cnt; j += 64) {
-      const Edge e = E[first + j];
-      const double qv = e.N ? e.W / (double)e.N : 0.0;
-      const double u = g.c_puct * e.prior * sq / (double)(1 + e.N);
-      const double v = qv + u;
-      if (v > best_v) {  // within a lane j increases: strict > keeps the first
-        best_v = v;
-        best = j;
+    if (NOISE && depth == 0) {  // (a constant false without NOISE: none of this is compiled in)
+      NoiseSmem& sm = *nsm;
+      bool drawn = cnt <= AZ_CHESS_MAX_MOVES;
+      if (!drawn) {
+        if (lane == 0) flag(t, az::kErrIllegal);
+      } else if (t.noise_in) {  // the caller's rows (wave-uniform)
+        if (lane == 0) sm.row = t.noise_cur[s]++;
+        __syncthreads();
+        const int row = sm.row;
+        if (row >= t.noise_rows) {
+          if (lane == 0) flag(t, az::kErrNoise);
+          drawn = false;
+        } else {
+          const double* src = t.noise_in + ((size_t)s * t.noise_rows + row) * AZ_CHESS_MAX_MOVES;
+          for (int j = lane; j < cnt; j += 64) sm.d[j] = src[j];
+          __syncthreads();
+        }
+      } else {
+        drawn = dirichlet_wave(g, t, s, lane, cnt, sm);
       }
-    }
+      if (!drawn) {  // the search fails (check_errors); the slot queues no leaf
+        if (lane == 0) t.slot_q[s] = -1;
+        return;
+      }
+      const bool f64 = t.root_f64[s] != 0;
+      for (int j = lane; j < cnt; j += 64) {
+        const Edge e = E[first + j];
+        const double kept = f64 ? (1.0 - g.noise_ratio) * e.prior
+                                : (double)((float)(1.0 - g.noise_ratio) * (float)e.prior);
+        const double prior = kept + g.noise_ratio * sm.d[j];
+        const double qv = e.N ? e.W / (double)e.N : 0.0;
+        const double u = g.c_puct * prior * sq / (double)(1 + e.N);
+        const double v = qv + u;
+        if (best == 1 << 30 || argmax_before(v, j, best_v, best)) {
+          best_v = v;
+          best = j;
+        }
+      }
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const double ov = __shfl_xor(best_v, off, 64);
-      const int oj = __shfl_xor(best, off, 64);
-      if (ov > best_v || (ov == best_v && oj < best)) {  // np.argmax: first maximum
-        best_v = ov;
-        best = oj;
+      for (int off = 32; off > 0; off >>= 1) {
+        const double ov = __shfl_xor(best_v, off, 64);
+        const int oj = __shfl_xor(best, off, 64);
+        // a lane without an edge (1 << 30) ranks below every edge
+        if (oj != 1 << 30 && (best == 1 << 30 || argmax_before(ov, oj, best_v, best))) {
+          best_v = ov;
+          best = oj;
+        }
+      }
+    } else {
+      for (int j = lane; j < cnt; j += 64) {
+        const Edge e = E[first + j];
+        const double qv = e.N ? e.W / (double)e.N : 0.0;
+        const double u = g.c_puct * e.prior * sq / (double)(1 + e.N);
+        const double v = qv + u;
+        if (v > best_v) {  // within a lane j increases: strict > keeps the first
+          best_v = v;
+          best = j;
+        }
+      }
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) {
+        const double ov = __shfl_xor(best_v, off, 64);
+        const int oj = __shfl_xor(best, off, 64);
+        if (ov > best_v || (ov == best_v && oj < best)) {  // np.argmax: first maximum
+          best_v = ov;
+          best = oj;
+        }
       }
     }
     if (depth >= g.max_depth) {
@@ -769,7 +949,7 @@ __device__ __forceinline__ void select_slot(const CCfg& g, const CTree& t, const
     ++depth;
     play(q, (uint16_t)e.action, true);  // Board.play(keep_same_player=True)
     first = e.child;
-    cnt = e.child < 0 ? 0 : e.child_n;
+    cnt = e.child < 0 ? 0 : (NOISE ? e.child_n & kChildMask : e.child_n);
     sum_next = e.N - 1;
   }
   if (lane == 0) {
@@ -778,19 +958,28 @@ __device__ __forceinline__ void select_slot(const CCfg& g, const CTree& t, const
   }
   leaf_body(g, t, c, s, lane, q, cand);
 }
-template <bool FUSED>
+template <bool FUSED, bool NOISE>
 __global__ __launch_bounds__(64) void select_kernel(CCfg g, CTree t, ChessCache c, const float* __restrict__ probs,
                                                     const float* __restrict__ values) {
   __shared__ uint16_t cand[AZ_CHESS_MAX_MOVES];
   __shared__ ExpandSmem esm;
+  NoiseSmem* nsm = nullptr;
+  if constexpr (NOISE) {
+    __shared__ NoiseSmem noise_smem;
+    nsm = &noise_smem;
+  }
   // the next simulation's queue counters (this one's were zeroed by the last
   // simulation's launch; a memset launch per simulation cost 5 us)
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     *t.next_count = 0;
     if (t.next_dup) *t.next_dup = 0;
   }
-  select_slot<FUSED>(g, t, c, probs, values, cand, esm);
-  dup_tail(t, c, threadIdx.x);
+  select_slot<FUSED, NOISE>(g, t, c, probs, values, cand, esm, nsm);
+  if constexpr (NOISE) {
+    [[clang::always_inline]] dup_tail(t, c, threadIdx.x);
+  } else {
+    dup_tail(t, c, threadIdx.x);
+  }
 }
 
 // Board.full_state of the queued leaves into the network input [q][64][128]:
@@ -959,7 +1148,9 @@ __global__ __launch_bounds__(64) void play_kernel(CCfg g, CTree t, CSamples smp,
   }
   __syncthreads();
   const int c_idx = chosen;
-  const Edge c = E[first + c_idx];
+  Edge c = E[first + c_idx];
+  const int c_f64 = (c.child_n & kChildF64) != 0;  // the new root's prior form (noise engines)
+  c.child_n &= kChildMask;
   // sample record (MCTS.play return_details: parent state, policy, move)
   if (tree_api) {
     const size_t r = (size_t)s;
@@ -1000,7 +1191,7 @@ __global__ __launch_bounds__(64) void play_kernel(CCfg g, CTree t, CSamples smp,
     int need = 0;
     if (j < top0) {
       e = D[j];
-      if (e.child >= 0) need = e.child_n;
+      if (e.child >= 0) need = e.child_n & kChildMask;
     }
     int incl = need;
 #pragma unroll
@@ -1034,6 +1225,7 @@ __global__ __launch_bounds__(64) void play_kernel(CCfg g, CTree t, CSamples smp,
     t.top[s] = overflow ? 0 : top;
     t.root_first[s] = 0;
     t.root_n[s] = (c.child >= 0 && !overflow) ? c.child_n : 0;
+    t.root_f64[s] = c_f64;
     t.ply[s] = ply + 1;
     t.initial[s] = 0;
     atomicAdd(t.stats + az::kStatPlies, 1ull);
@@ -1122,6 +1314,9 @@ struct az_chess_engine {
   int16_t* tree_pol_a = nullptr;
   double* tree_pol_p = nullptr;
   az_chess_pos* tree_roots = nullptr;
+  double* noise_buf = nullptr;  // az_chess_tree_search_noise: the caller's root-noise rows
+  size_t noise_cap = 0;
+  int32_t* noise_cur = nullptr;
   // AZ_EVAL_HOST: the callback and its pinned staging buffers (slots leaves)
   az_eval_fn host_fn = nullptr;
   void* host_user = nullptr;
@@ -1192,8 +1387,14 @@ int simulate(az_chess_engine* e, CLane& L) {
   L.t.next_dup = L.counts + 2 * (L.par ^ 1) + 1;
   L.par ^= 1;
   L.t.epoch += 1;  // a fresh dedup table (tags of older epochs read as empty)
-  if (L.pending_expand) select_kernel<true><<<S, 64, 0, s>>>(L.g, L.t, e->cache, L.probs, L.values);
-  else select_kernel<false><<<S, 64, 0, s>>>(L.g, L.t, e->cache, nullptr, nullptr);
+  if (L.g.noise) {  // the root-noise instantiations (the default path carries none of their code)
+    if (L.pending_expand) select_kernel<true, true><<<S, 64, 0, s>>>(L.g, L.t, e->cache, L.probs, L.values);
+    else select_kernel<false, true><<<S, 64, 0, s>>>(L.g, L.t, e->cache, nullptr, nullptr);
+  } else if (L.pending_expand) {
+    select_kernel<true, false><<<S, 64, 0, s>>>(L.g, L.t, e->cache, L.probs, L.values);
+  } else {
+    select_kernel<false, false><<<S, 64, 0, s>>>(L.g, L.t, e->cache, nullptr, nullptr);
+  }
   if (L.g.evaluator == AZ_EVAL_NETWORK) {
     // the one-launch tower builds the leaves' input planes itself (no encode
     // launch on the chain; az_nn.h TowerLeaves); the other forms read rows
@@ -1257,6 +1458,7 @@ int make_lane(az_chess_engine* e, CLane* L, int first, int n) {
   t.root += f;
   t.root_first += f;
   t.root_n += f;
+  t.root_f64 += f;
   t.half += f;
   t.top += f;
   t.ply += f;
@@ -1319,6 +1521,9 @@ int az_chess_engine_create(int device, const az_chess_config* cfg, az_chess_engi
     return az::fail_abi(AZ_E_INVALID, "negative bound");
   if ((int64_t)c.slots * 64 * 512 >= (1ll << 31))
     return az::fail_abi(AZ_E_INVALID, "slots * 64 * 512 must stay below 2^31 (32-bit activation byte offsets)");
+  if (c.dirichlet_noise && !(c.dirichlet_alpha > 0.0 && c.dirichlet_alpha <= 1.0 && std::isfinite(c.dirichlet_ratio)))
+    return az::fail_abi(AZ_E_INVALID, "Dirichlet noise needs 0 < dirichlet_alpha <= 1 (the reference's 0.03) and a "
+                                      "finite dirichlet_ratio");
   AZ_TRY(az::open_device(device));
   AZ_HIP(upload_rays());
   az_chess_engine* e = new az_chess_engine();
@@ -1330,6 +1535,9 @@ int az_chess_engine_create(int device, const az_chess_config* cfg, az_chess_engi
   g.greedy_ply = c.index_move_greedy;
   g.c_puct = c.exploration_constant;
   g.evaluator = c.evaluator;
+  g.noise = c.dirichlet_noise != 0;
+  g.noise_alpha = c.dirichlet_alpha;
+  g.noise_ratio = c.dirichlet_ratio;
   g.max_plies = c.max_plies > 0 ? c.max_plies : 512;
   g.max_depth = 512;
   const int64_t half = c.arena_edges > 0 ? c.arena_edges : (int64_t)96 * c.mcts_iterations + 256;
@@ -1350,7 +1558,8 @@ int az_chess_engine_create(int device, const az_chess_config* cfg, az_chess_engi
   CTree& t = e->t;
   int rc;
   if ((rc = e->mem.alloc(&t.edges, S * 2 * (size_t)g.half_cap, false)) || (rc = e->mem.alloc(&t.root, S, false)) ||
-      (rc = e->mem.alloc(&t.root_first, S, false)) || (rc = e->mem.alloc(&t.root_n, S, false)) || (rc = e->mem.alloc(&t.half, S, false)) ||
+      (rc = e->mem.alloc(&t.root_first, S, false)) || (rc = e->mem.alloc(&t.root_n, S, false)) || (rc = e->mem.alloc(&t.root_f64, S, false)) ||
+      (rc = e->mem.alloc(&t.half, S, false)) ||
       (rc = e->mem.alloc(&t.top, S, false)) || (rc = e->mem.alloc(&t.ply, S, false)) || (rc = e->mem.alloc(&t.initial, S, false)) ||
       (rc = e->mem.alloc(&t.game_id, S, false)) || (rc = e->mem.alloc(&t.path, S * g.max_depth, false)) ||
       (rc = e->mem.alloc(&t.path_len, S, false)) || (rc = e->mem.alloc(&t.leaf, S, false)) ||
@@ -1761,12 +1970,55 @@ int az_chess_tree_release(az_chess_engine* e, int n, const int32_t* slots) {
 
 int az_chess_tree_search(az_chess_engine* e, int n_sims) {
   if (!e || n_sims < 0) return az::fail_abi(AZ_E_INVALID, "bad arguments");
+  if (e->g.noise)  // the tree API's noise is drawn by the caller from numpy's global stream
+    return az::fail_abi(AZ_E_INVALID, "this engine mixes Dirichlet root noise: search it with "
+                                      "az_chess_tree_search_noise (the caller's np.random.dirichlet draws)");
   int rc;
   if ((rc = ready_to_search(e))) return rc;
   AZ_HIP(hipSetDevice(e->device));
   for (int s = 0; s < n_sims; ++s)
     for (CLane* L : e->lanes)
       if ((rc = simulate(e, *L))) return rc;
+  for (CLane* L : e->lanes)
+    if ((rc = flush_expand(*L))) return rc;
+  if ((rc = sync_lanes(e))) return rc;
+  return check_errors(e);
+}
+
+int az_chess_tree_search_noise(az_chess_engine* e, int n_sims, const double* noise, int rows) {
+  if (!e || n_sims < 0 || rows < 0 || (rows > 0 && !noise)) return az::fail_abi(AZ_E_INVALID, "bad arguments");
+  if (!e->g.noise)
+    return az::fail_abi(AZ_E_INVALID, "az_chess_tree_search_noise needs an engine created with dirichlet_noise = 1");
+  int rc;
+  if ((rc = ready_to_search(e))) return rc;
+  AZ_HIP(hipSetDevice(e->device));
+  if ((rc = sync_lanes(e))) return rc;
+  const size_t S = (size_t)e->g.slots, M = AZ_CHESS_MAX_MOVES, n = S * (size_t)std::max(rows, 1) * M;
+  if (n > e->noise_cap) {  // grown on demand, kept for the next searches
+    double* buf = nullptr;
+    if ((rc = e->mem.alloc(&buf, n, false))) return rc;
+    e->noise_buf = buf;
+    e->noise_cap = n;
+  }
+  if (!e->noise_cur && (rc = e->mem.alloc(&e->noise_cur, S, false))) return rc;
+  if (rows) AZ_HIP(hipMemcpyAsync(e->noise_buf, noise, S * rows * M * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  AZ_HIP(hipMemsetAsync(e->noise_cur, 0, S * sizeof(int32_t), e->stream));
+  AZ_HIP(hipStreamSynchronize(e->stream));
+  for (CLane* L : e->lanes) {
+    L->t.noise_in = e->noise_buf + (size_t)L->first * rows * M;
+    L->t.noise_cur = e->noise_cur + L->first;
+    L->t.noise_rows = rows;
+  }
+  rc = 0;
+  for (int s = 0; s < n_sims && !rc; ++s)
+    for (CLane* L : e->lanes)
+      if ((rc = simulate(e, *L))) break;
+  for (CLane* L : e->lanes) {  // self-play keeps drawing on the device
+    L->t.noise_in = nullptr;
+    L->t.noise_cur = nullptr;
+    L->t.noise_rows = 0;
+  }
+  if (rc) return rc;
   for (CLane* L : e->lanes)
     if ((rc = flush_expand(*L))) return rc;
   if ((rc = sync_lanes(e))) return rc;
@@ -1848,7 +2100,7 @@ int az_chess_tree_export(az_chess_engine* e, int slot, double* prior, double* w,
     if (w) w[i] = h[i].W;
     if (n) n[i] = h[i].N;
     if (child) child[i] = h[i].child;
-    if (child_n) child_n[i] = h[i].child_n;
+    if (child_n) child_n[i] = h[i].child_n & kChildMask;
     if (moves) moves[i] = (uint16_t)h[i].action;
     if (child_value) child_value[i] = h[i].child_value;
   }

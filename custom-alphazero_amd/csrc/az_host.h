@@ -98,6 +98,7 @@ inline int device_error_status(unsigned long long* stats, const ErrorHints& hint
   if (err & kErrIllegal) m += " illegal-move";
   if (err & kErrNoRoot) m += " play-before-search";
   if (err & kErrNoise) m += " root-noise-rows-exhausted(pass a row per root selection)";
+  if (err & kErrDraw) m += " root-noise-draw-round-cap(a defect in the device Dirichlet draw or a corrupt stream position)";
   if (err & kErrActRange)
     m += " activation-range(a non-finite activation, or |x| > 32752 in the per-layer fp16x2 convs: "
          "use conv_algo=AZ_CONV_F16X2 or AZ_CONV_DIRECT)";

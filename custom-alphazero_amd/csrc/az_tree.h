@@ -47,7 +47,8 @@ constexpr int kCountWords = 2 * 4 * kCountStride;
 enum : unsigned long long {
   kErrArena = 1, kErrPow = 2, kErrPath = 4, kErrIllegal = 8, kErrNoRoot = 16,
   kErrActRange = 32,  // a conv16 activation beyond the split16 range (|x| > 32752)
-  kErrNoise = 64      // the tree API's host-drawn root noise ran out of rows
+  kErrNoise = 64,     // the tree API's host-drawn root noise ran out of rows
+  kErrDraw = 128      // the wave-parallel Dirichlet draw hit its round cap (az_dirichlet_wave.h)
 };
 
 // All device state of a forest (struct of arrays over slots).

@@ -120,8 +120,12 @@ def check_mcts_config(path: str = "tree"):
     games own their np.random streams on the device, MT19937 seeded like
     self_play.py:45) and in the Connect-N tree API and arena (path "tree":
     the caller's np.random.dirichlet draws, az_tree_search_noise).  Chess
-    (path "chess") has no root noise: the reference's chess MCTS cannot run
-    (chess/board.py:178 vs mcts.py:179), so there is no behaviour to match."""
+    self-play (path "chess_selfplay": self_play.play / play_chess / play_game)
+    draws it the same way, on the device from each game's MT19937 stream; the
+    reference's chess MCTS cannot run (chess/board.py:178 vs mcts.py:179), but
+    the noisy selection is its game-agnostic code's.  The Python MCTS class on
+    a chess Board and the chess arena (path "chess") are not wired to the
+    engine's ChessEngine.tree_search(noise=) yet and refuse the flag."""
     if ConfigMCTS.enable_dirichlet_noise and path == "chess":
         raise NotImplementedError(
             "ConfigMCTS.enable_dirichlet_noise=True is not implemented for chess on the MI355X engine "

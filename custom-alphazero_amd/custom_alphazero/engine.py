@@ -49,7 +49,8 @@ class ChessConfig(ctypes.Structure):
         ("value_hidden", ctypes.c_int32), ("max_plies", ctypes.c_int32),
         ("bn_epsilon", ctypes.c_double), ("arena_edges", ctypes.c_int64),
         ("conv_algo", ctypes.c_int32), ("lanes", ctypes.c_int32), ("cache_log2", ctypes.c_int32),
-        ("reserved", ctypes.c_int32 * 5),
+        ("dirichlet_noise", ctypes.c_int32), ("dirichlet_alpha", ctypes.c_double),
+        ("dirichlet_ratio", ctypes.c_double),
     ]
 
 
@@ -109,7 +110,7 @@ EXPORTED = (
     "az_chess_forward", "az_chess_selfplay_begin", "az_chess_selfplay_step", "az_chess_selfplay_run",
     "az_chess_selfplay_results", "az_chess_selfplay_drain", "az_chess_stats", "az_chess_timer_enable",
     "az_chess_tree_reset",
-    "az_chess_tree_release", "az_chess_tree_search", "az_chess_tree_play", "az_chess_tree_info",
+    "az_chess_tree_release", "az_chess_tree_search", "az_chess_tree_search_noise", "az_chess_tree_play", "az_chess_tree_info",
     "az_chess_tree_export",
 )
 
@@ -192,6 +193,7 @@ def load_library():
         "az_chess_tree_reset": (ctypes.c_int, [P, ctypes.c_int, P, P]),
         "az_chess_tree_release": (ctypes.c_int, [P, ctypes.c_int, P]),
         "az_chess_tree_search": (ctypes.c_int, [P, ctypes.c_int]),
+        "az_chess_tree_search_noise": (ctypes.c_int, [P, ctypes.c_int, P, ctypes.c_int]),
         "az_chess_tree_play": (ctypes.c_int, [P, P, ctypes.c_int, ctypes.c_int, P, P, P, P, P]),
         "az_chess_tree_info": (ctypes.c_int, [P, ctypes.c_int, P, P]),
         "az_chess_tree_export": (ctypes.c_int, [P, ctypes.c_int, P, P, P, P, P, P, P]),
@@ -586,7 +588,12 @@ class ChessEngine:
     """libaz chess self-play engine (include/az_chess.h): `slots` concurrent
     chess games on one device, MCTS with the policy/value network on the
     (8, 8, 118) Board.full_state planes and the 1880-move action space -- or,
-    with evaluator=EVAL_HOST, with any Python callable (set_host_evaluator)."""
+    with evaluator=EVAL_HOST, with any Python callable (set_host_evaluator).
+
+    dirichlet_noise: ConfigMCTS.enable_dirichlet_noise (root noise, reference
+    mcts.py:70-85) with dirichlet_alpha / dirichlet_ratio.  Self-play draws
+    it on the device from each game's MT19937 stream, bit for bit numpy's
+    legacy RandomState.dirichlet; tree_search takes the caller's draws."""
 
     ACTIONS = 1880
     MAX_MOVES = 256
@@ -594,7 +601,8 @@ class ChessEngine:
     def __init__(self, mcts_iterations=800, slots=256, evaluator=EVAL_NETWORK, max_plies=512,
                  index_move_greedy=8, exploration_constant=1.5, filters=128, depth=4,
                  value_hidden=256, bn_epsilon=1e-3, arena_edges=0, conv_algo=CONV_F16X2,
-                 device=0, lanes=0, cache_log2=0):
+                 device=0, lanes=0, cache_log2=0, dirichlet_noise=False, dirichlet_alpha=0.03,
+                 dirichlet_ratio=0.25):
         L = load_library()
         self.slots, self.mcts_iterations = slots, mcts_iterations
         self.max_plies = max_plies if max_plies > 0 else 512
@@ -602,7 +610,9 @@ class ChessEngine:
                           exploration_constant=exploration_constant, slots=slots,
                           evaluator=evaluator, filters=filters, depth=depth,
                           value_hidden=value_hidden, max_plies=max_plies, bn_epsilon=bn_epsilon,
-                          arena_edges=arena_edges, conv_algo=conv_algo, lanes=lanes, cache_log2=cache_log2)
+                          arena_edges=arena_edges, conv_algo=conv_algo, lanes=lanes, cache_log2=cache_log2,
+                          dirichlet_noise=int(bool(dirichlet_noise)), dirichlet_alpha=float(dirichlet_alpha),
+                          dirichlet_ratio=float(dirichlet_ratio))
         handle = ctypes.c_void_p()
         _check(L.az_chess_engine_create(int(device), ctypes.byref(cfg), ctypes.byref(handle)))
         self._h, self._L, self._n_games = handle, L, 0
@@ -757,8 +767,18 @@ class ChessEngine:
         slots = np.ascontiguousarray(slots, np.int32)
         _check(self._L.az_chess_tree_release(self._h, len(slots), _ptr(slots)))
 
-    def tree_search(self, n_sims):
-        self._search_call(self._L.az_chess_tree_search(self._h, int(n_sims)))
+    def tree_search(self, n_sims, noise=None):
+        """noise (engines made with dirichlet_noise): [slots, rows, 256] float64,
+        row r of slot s the np.random.dirichlet vector its r-th root selection
+        mixes in, entry i for root edge i (az_chess_tree_search_noise)."""
+        if noise is None:
+            self._search_call(self._L.az_chess_tree_search(self._h, int(n_sims)))
+            return
+        noise = np.ascontiguousarray(noise, np.float64)
+        if noise.ndim != 3 or noise.shape[0] != self.slots or noise.shape[2] != self.MAX_MOVES:
+            raise ValueError(f"noise must be [slots={self.slots}, rows, {self.MAX_MOVES}], got {noise.shape}")
+        self._search_call(self._L.az_chess_tree_search_noise(self._h, int(n_sims), _ptr(noise),
+                                                             int(noise.shape[1])))
 
     def tree_play(self, uniforms=None, greedy=False, deterministic=False):
         """-> moves [S] (move codes, -1 idle), status [S] (AZ_CHESS_* of the new

@@ -29,8 +29,10 @@ chess arena game:
 * the models alternate as in evaluate.py:39, 61-62, 75-83;
 * a model is a PolicyValueModel (a network engine) or, under MCTS, any other
   callable model(x) -> (probabilities, value) (a host-evaluator engine);
-* Dirichlet root noise stays refused (check_mcts_config("chess")), and `trace`
-  collects the final boards' az_chess_pos records.
+* Dirichlet root noise stays refused here (check_mcts_config("chess"): the
+  chess engine has it in self-play and as ChessEngine.tree_search(noise=),
+  which this arena is not wired to yet), and `trace` collects the final
+  boards' az_chess_pos records.
 The batched chess arena searches each ply with az_chess_tree_release /
 _reset / _search / _play; its raw-policy mode encodes every live board in one
 batched kernels.encode.  deterministic=True gives the sequential loop's

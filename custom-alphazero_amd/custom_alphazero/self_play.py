@@ -152,13 +152,16 @@ def _chess_evaluator(model):
 
 
 def _chess_engine(model, n_slots, sims):
-    check_mcts_config("chess")
+    check_mcts_config("chess_selfplay")
     evaluator = _chess_evaluator(model)
     synthetic = evaluator == az.EVAL_SYNTHETIC
+    # root noise: drawn on the device from each game's own stream (az_chess.h)
+    noise = (bool(ConfigMCTS.enable_dirichlet_noise), ConfigMCTS.dirichlet_noise_value,
+             ConfigMCTS.dirichlet_noise_ratio)
     # a callable is part of the key by identity: another callable gets another engine
     key = (sims, n_slots, synthetic, ConfigMCTS.index_move_greedy, ConfigMCTS.exploration_constant,
            ConfigModel.depth, ConfigSelfPlay.chess_max_plies, ConfigSelfPlay.chess_cache_log2,
-           id(model) if evaluator == az.EVAL_HOST else None)
+           id(model) if evaluator == az.EVAL_HOST else None, noise)
     eng = _CHESS_ENGINES.get(key)
     if eng is not None and evaluator == az.EVAL_HOST and eng.host_model is not model:
         eng = None  # (an id reused by a new object)
@@ -169,7 +172,8 @@ def _chess_engine(model, n_slots, sims):
                              exploration_constant=ConfigMCTS.exploration_constant,
                              filters=ConfigModel.filters, depth=ConfigModel.depth,
                              value_hidden=ConfigModel.value_hidden, bn_epsilon=ConfigModel.bn_epsilon,
-                             cache_log2=ConfigSelfPlay.chess_cache_log2)
+                             cache_log2=ConfigSelfPlay.chess_cache_log2,
+                             dirichlet_noise=noise[0], dirichlet_alpha=noise[1], dirichlet_ratio=noise[2])
         eng.weights_key = None
         eng.host_model = None
         if evaluator == az.EVAL_HOST:
@@ -236,7 +240,7 @@ def play(run_id: str, plays_inferences: Optional[Dict[str, Tuple[np.ndarray, flo
     if base_seed is None:
         base_seed = int(time.time()) % (2 ** 32 - 1)
     if ConfigGeneral.game == "chess":
-        return play_chess(model, n_games, base_seed, first_game)
+        return play_chess(model, n_games, base_seed, first_game, sims)
     eng = _batched_engine(model, min(n_games, ConfigSelfPlay.concurrent_games), sims)
     if ConfigSelfPlay.cache_log2 and (plays_inferences is None
                                       or plays_inferences is not _CACHE_OWNER["dict"]):

@@ -120,14 +120,26 @@ typedef struct az_chess_config {
                                      (the masked priors, up to 256, and the value); identical leaves
                                      of one simulation share a network row.  0 = off, else 4..28;
                                      results are identical either way */
-    int32_t reserved[5];
+    int32_t dirichlet_noise;      /* ConfigMCTS.enable_dirichlet_noise (mcts.py:70-85, 113-116); the
+                                     three fields took the place of reserved[5] (all zero = off, as
+                                     every earlier caller passed), so the ABI version did not move */
+    double dirichlet_alpha;       /* ConfigMCTS.dirichlet_noise_value (0.03); 0 < alpha <= 1 */
+    double dirichlet_ratio;       /* ConfigMCTS.dirichlet_noise_ratio (0.25) */
 } az_chess_config;
-/* Scope: no Dirichlet root noise (ConfigMCTS.enable_dirichlet_noise,
- * mcts.py:70-85) in the chess engine.  The reference's chess MCTS cannot run
- * a search at all (chess/board.py:178's get_result signature vs mcts.py:179),
- * so there is no noisy chess behaviour to match; the Python layer refuses
- * the flag for chess (config.check_mcts_config("chess")) instead of
- * ignoring it.  Connect-N has it in self-play and in the tree API (az.h).
+/* Dirichlet root noise (dirichlet_noise = 1): every selection at the current
+ * root of a tree that has edges draws np.random.dirichlet(alpha * ones(k)), k
+ * the root's edge count, and takes np.argmax (NaN first) of the UCB over
+ * (1 - ratio) * priors + ratio * noise, computed as numpy does (the first
+ * product in the priors' dtype: float32, or float64 after
+ * normalize_probabilities' uniform branch).  The reference's chess MCTS cannot
+ * run a search (chess/board.py:178's get_result signature vs mcts.py:179), but
+ * this behaviour is its game-agnostic code's.  Self-play draws on the device
+ * from the game's stream, MT19937(base_seed + game_id), bit for bit numpy's
+ * legacy RandomState.dirichlet: all of a move's root-noise vectors in
+ * simulation order, then MCTS.play's one random_sample.  The tree API takes
+ * the caller's draws (az_chess_tree_search_noise).  The Python MCTS class on a
+ * chess Board and the chess arena still refuse the flag
+ * (config.check_mcts_config("chess")).
  * Evaluators: the network (AZ_EVAL_NETWORK), the oracle's synthetic function
  * (AZ_EVAL_SYNTHETIC) or a host callback (AZ_EVAL_HOST,
  * az_chess_engine_set_evaluator): self-play, the tree API and, in Python,
@@ -217,8 +229,19 @@ int az_chess_stats(az_chess_engine* eng, az_stats* st);
 int az_chess_tree_reset(az_chess_engine* eng, int n, const int32_t* slots, const az_chess_pos* roots);
 /* Idle the given slots (search and play skip them) until the next reset. */
 int az_chess_tree_release(az_chess_engine* eng, int n, const int32_t* slots);
-/* MCTS.search(n_sims) on every active slot. */
+/* MCTS.search(n_sims) on every active slot.  AZ_E_INVALID on an engine
+ * created with dirichlet_noise (its searches need the caller's draws). */
 int az_chess_tree_search(az_chess_engine* eng, int n_sims);
+/* The same on an engine created with dirichlet_noise = 1 (AZ_E_INVALID on any
+ * other): noise [slots][rows][AZ_CHESS_MAX_MOVES] f64, row r of slot s the
+ * np.random.dirichlet vector that slot's r-th root selection of this search
+ * mixes in; entry i of a row belongs to root edge i (python-chess move order),
+ * entries past the root's edge count are ignored.  One row is consumed per
+ * simulation whose root has edges (the first simulation after a reset expands
+ * the root and consumes none); a slot that runs out of rows fails the search
+ * with AZ_E_DEVICE (root-noise-rows-exhausted).  Added without a version bump:
+ * the change only adds. */
+int az_chess_tree_search_noise(az_chess_engine* eng, int n_sims, const double* noise, int rows);
 /* MCTS.play(greedy, deterministic) on every active slot: uniforms [slots] are
  * the np.random.random_sample draws np.random.choice consumes (ignored when
  * deterministic).  Per slot: moves (move code, -1 idle), status (AZ_CHESS_*
