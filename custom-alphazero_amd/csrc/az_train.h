@@ -1,5 +1,7 @@
-// az_train.h -- the training step of the Connect-N policy/value network
-// (az_trainer_* in include/az.h): shapes and launchers of csrc/az_train.hip.
+// az_train.h -- the training step of the policy/value network, Connect-N
+// (4 input planes, at most 128 actions) and chess (118 planes, 1880 actions):
+// az_trainer_* in include/az.h, az_chess_trainer_create in include/az_chess.h;
+// shapes and launchers of csrc/az_train.hip.
 //
 // Everything is fp32.  Activations are NHWC rows [n*HW][C]; weights stay in
 // their Keras layouts (kernel [tap][cin][cout], dense [in][out]) inside one
@@ -20,6 +22,9 @@ constexpr int kRowsPerPart = 64;     // rows one workgroup reduces in a two-stag
 constexpr int kBoardsPerPart = 8;    // boards one split-K part of a weight gradient covers
 constexpr int kMaxCellsTrain = 128;  // H*W the engine accepts (az_device.h kMaxCells)
 constexpr int kMaxHidden = 1024;     // ValueHead hidden_dim the heads kernel holds in LDS
+constexpr int kChessPlanes = 118;    // Board.full_state's planes (include/az_chess.h AZ_CHESS_PLANES)
+constexpr int kChessActions = 1880;  // AZ_CHESS_ACTIONS
+constexpr int kChessCells = 64;
 
 // The factor the moving variance applies to the batch's biased variance
 // (TF's fused BatchNormalization feeds the moving average Bessel's corrected
@@ -45,6 +50,12 @@ void conv_wgrad(hipStream_t s, const Geo& g, int taps, const float* x, const flo
                 int n);
 void stem_forward(hipStream_t s, const Geo& g, const float* x, const float* w, const float* bias, float* y, int rows);
 void stem_wgrad(hipStream_t s, const Geo& g, const float* x, const float* dy, float* partial, float* dw, int rows);
+// the chess stem, 118 -> F on the fp32 MFMA: x [rows][118] as the caller gave it (no padded copy);
+// dw [9][118][F], partial: board_parts(n) * 9 * 118 * F floats.  The stem has no data gradient.
+void chess_stem_forward(hipStream_t s, const Geo& g, const float* x, const float* w, const float* bias, float* y,
+                        int rows);
+void chess_stem_wgrad(hipStream_t s, const Geo& g, const float* x, const float* dy, float* partial, float* dw,
+                      int n);
 void headconv_forward(hipStream_t s, const float* h, const float* wp, const float* bp, const float* wv,
                       const float* bv, float* yp, float* yv, int rows);
 void headconv_wgrad(hipStream_t s, const float* h, const float* dyp, const float* dyv, float* partial, float* dwp,
@@ -75,17 +86,22 @@ struct HeadsArgs {
   float *ghp, *ghv;                // gradients of hp, hv
   float *lossp, *lossv;            // per board
 };
-void heads_forward_backward(hipStream_t s, const Geo& g, const HeadsArgs& a, int n);
+void heads_forward_backward(hipStream_t s, const Geo& g, const HeadsArgs& a, int n);  // A <= 128
+// the same for the chess heads (HW = 64, A = 1880): the policy head spread over the workgroup
+void chess_heads_forward_backward(hipStream_t s, const Geo& g, const HeadsArgs& a, int n);
 // dw[i][j] = sum_b x[b][i] d[b][j], db[j] = sum_b d[b][j]
 void dense_wgrad(hipStream_t s, const float* x, const float* d, float* dw, float* db, int n, int I, int J);
+// the same sums for the chess policy layer (I = 128, J = 1880), each dlogit loaded once for eight inputs
+void chess_policy_wgrad(hipStream_t s, const float* x, const float* d, float* dw, float* db, int n);
 // losses[3] = total, policy, value; sq_partial: (n_l2 + 4095) / 4096 doubles
 void losses(hipStream_t s, const float* w, int64_t n_l2, double l2, const float* lossp, const float* lossv, int n,
             double* sq_partial, float* out);
 // g += 2*l2*w on the first n_l2 elements (the .kernel tensors); a = mom*a - lr*g; w += a
 void sgd_update(hipStream_t s, float* w, float* g, float* m, int64_t n_train, int64_t n_l2, float lr, float mom,
                 float l2);
-// moving = m*moving + (1-m)*batch*factor; means then variances, n_stats each
-void moving_update(hipStream_t s, float* moving, const float* batch, int64_t n_stats, float m, float var_factor);
+// moving = m*moving + take*batch*factor, take = 1 - m as the caller rounds it; means then variances, n_stats each
+void moving_update(hipStream_t s, float* moving, const float* batch, int64_t n_stats, float m, float take,
+                   float var_factor);
 
 }  // namespace train
 }  // namespace az

@@ -111,7 +111,7 @@ EXPORTED = (
     "az_chess_selfplay_results", "az_chess_selfplay_drain", "az_chess_stats", "az_chess_timer_enable",
     "az_chess_tree_reset",
     "az_chess_tree_release", "az_chess_tree_search", "az_chess_tree_search_noise", "az_chess_tree_play", "az_chess_tree_info",
-    "az_chess_tree_export",
+    "az_chess_tree_export", "az_chess_trainer_create",
 )
 
 _lib = None
@@ -197,6 +197,8 @@ def load_library():
         "az_chess_tree_play": (ctypes.c_int, [P, P, ctypes.c_int, ctypes.c_int, P, P, P, P, P]),
         "az_chess_tree_info": (ctypes.c_int, [P, ctypes.c_int, P, P]),
         "az_chess_tree_export": (ctypes.c_int, [P, ctypes.c_int, P, P, P, P, P, P, P]),
+        "az_chess_trainer_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ChessConfig), ctypes.c_int,
+                                                   ctypes.POINTER(P)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -516,10 +518,13 @@ TRAIN_WEIGHT, TRAIN_GRAD, TRAIN_MOMENTUM = 0, 1, 2  # include/az.h AZ_TRAIN_*
 
 class Trainer:
     """One libaz trainer (az_trainer_*, csrc/az_train.hip): the training step
-    of the Connect-N policy/value network -- forward with batch statistics,
-    backward, SGD with momentum -- on one device and a stream of its own.  It
-    owns its weights, gradients and momentum; tensors go in and out by their
-    weights.weight_spec names in Keras layout."""
+    of the policy/value network -- forward with batch statistics, backward,
+    SGD with momentum -- on one device and a stream of its own.  It owns its
+    weights, gradients and momentum; tensors go in and out by their
+    weights.weight_spec names in Keras layout.  This class is the Connect-N
+    network's (4 input planes); ChessTrainer below is the chess network's."""
+
+    planes = 4
 
     def __init__(self, height=6, width=7, gravity=True, max_batch=256, filters=128, depth=4,
                  value_hidden=256, bn_epsilon=1e-3, device=0):
@@ -529,7 +534,7 @@ class Trainer:
         self.action_space = self.width if self.gravity else self.width * self.height
         self.max_batch = int(max_batch)
         self.spec = weight_spec(self.height, self.width, self.action_space, filters, max(int(depth), 0),
-                                value_hidden, 4)
+                                value_hidden, self.planes)
         cfg = Config(board_height=self.height, board_width=self.width, n=min(4, self.height, self.width),
                      gravity=int(self.gravity), filters=filters, depth=depth, value_hidden=value_hidden,
                      bn_epsilon=bn_epsilon)
@@ -572,9 +577,9 @@ class Trainer:
         return {n: self.read(n, what) for n in names}
 
     def step(self, x, pi, z, lr, momentum=0.9, l2=1e-4, bn_momentum=0.99):
-        """One SGD step on the batch x [n, H, W, 4], pi [n, A], z [n]; returns
+        """One SGD step on the batch x [n, H, W, planes], pi [n, A], z [n]; returns
         (total, policy, value) losses of the weights before the update."""
-        x = np.ascontiguousarray(x, np.float32).reshape(-1, self.height, self.width, 4)
+        x = np.ascontiguousarray(x, np.float32).reshape(-1, self.height, self.width, self.planes)
         n = len(x)
         pi = np.ascontiguousarray(pi, np.float32).reshape(n, self.action_space)
         z = np.ascontiguousarray(z, np.float32).reshape(n)
@@ -582,6 +587,28 @@ class Trainer:
         _check(self._L.az_trainer_step(self._h, _ptr(x), _ptr(pi), _ptr(z), n, float(lr), float(momentum),
                                        float(l2), float(bn_momentum), _ptr(losses)))
         return float(losses[0]), float(losses[1]), float(losses[2])
+
+
+class ChessTrainer(Trainer):
+    """The trainer of the chess network (az_chess_trainer_create): the
+    (8, 8, 118) Board.full_state planes and the 1880-move action space, with
+    Trainer's methods.  step takes x [n, 8, 8, 118], pi [n, 1880], z [n]."""
+
+    planes = 118
+
+    def __init__(self, max_batch=256, filters=128, depth=4, value_hidden=256, bn_epsilon=1e-3, device=0):
+        from custom_alphazero.model.weights import weight_spec
+        L = load_library()
+        self.height = self.width = 8
+        self.gravity = False
+        self.action_space = ChessEngine.ACTIONS
+        self.max_batch = int(max_batch)
+        self.spec = weight_spec(8, 8, self.action_space, filters, max(int(depth), 0), value_hidden, self.planes)
+        cfg = ChessConfig(filters=filters, depth=depth, value_hidden=value_hidden, bn_epsilon=bn_epsilon)
+        handle = ctypes.c_void_p()
+        _check(L.az_chess_trainer_create(int(device), ctypes.byref(cfg), self.max_batch, ctypes.byref(handle)))
+        self._h = handle
+        self._L = L
 
 
 class ChessEngine:

@@ -8,9 +8,9 @@ model returns (probabilities [B, A], value [B, 1]) as torch CPU tensors, so
 the reference's `.numpy()` idiom (mcts.py:134-137) works unchanged.
 
 Training (model.fit on one batch, model/tensorflow/train.py:24-31) is
-train_on_batch: a lazily created engine.Trainer (az_trainer_*,
-csrc/az_train.hip) that keeps the weights, gradients and SGD momentum on the
-device.  After a step the trainer's weights are the model's: get_weights(),
+train_on_batch: a lazily created engine.Trainer, or engine.ChessTrainer for
+the chess network (az_trainer_*, az_chess_trainer_create, csrc/az_train.hip),
+that keeps the weights, gradients and SGD momentum on the device.  After a step the trainer's weights are the model's: get_weights(),
 hash, the inference call and save_with_meta all see them.  Momentum lives as
 long as the trainer and is not written to a checkpoint.
 """
@@ -152,18 +152,28 @@ class PolicyValueModel:
 
     # ------------------------------------------------------------ training
     def trainer(self):
-        """The model's engine.Trainer (created on first use, max_batch =
-        ConfigModel.batch_size), holding the model's current weights."""
+        """The model's trainer (created on first use, max_batch =
+        ConfigModel.batch_size), holding the model's current weights: an
+        engine.ChessTrainer for the chess network ((8, 8, 118) planes, 1880
+        actions), an engine.Trainer for a Connect-N network."""
+        if getattr(self, "weights", None) is None:
+            # a precondition of the call for either game: there is nothing to train (AZ_E_INVALID)
+            raise az.AzError("libaz error -1: PolicyValueModel.trainer(): the model has no weights "
+                             "(it was not constructed)")
         if self._trainer is None:
             H, W, C = self.input_dim
-            if C != 4 or self.action_space not in (W, H * W):
-                # chess (118 planes, 1880 actions) is out of the trainer's scope: AZ_E_INVALID
-                raise az.AzError("libaz error -1: the trainer implements the Connect-N network only "
-                                 f"(input planes {C}, action space {self.action_space})")
-            self._trainer = az.Trainer(H, W, gravity=self.action_space == W, max_batch=ConfigModel.batch_size,
-                                       filters=ConfigModel.filters, depth=self.depth,
-                                       value_hidden=ConfigModel.value_hidden,
-                                       bn_epsilon=ConfigModel.bn_epsilon, device=self.device.index or 0)
+            chess = self.input_dim == (8, 8, 118) and self.action_space == az.ChessEngine.ACTIONS
+            if not chess and (C != 4 or self.action_space not in (W, H * W)):
+                raise az.AzError("libaz error -1: the trainer implements the Connect-N network (4 input "
+                                 "planes, W or H*W actions) and the chess network (8x8x118 planes, 1880 "
+                                 f"actions), not input {self.input_dim} with action space {self.action_space}")
+            common = dict(max_batch=ConfigModel.batch_size, filters=ConfigModel.filters, depth=self.depth,
+                          value_hidden=ConfigModel.value_hidden, bn_epsilon=ConfigModel.bn_epsilon,
+                          device=self.device.index or 0)
+            if chess:
+                self._trainer = az.ChessTrainer(**common)
+            else:
+                self._trainer = az.Trainer(H, W, gravity=self.action_space == W, **common)
         if self._trainer_version != self._version:
             self._trainer.set_weights(self.engine_weights())
             self._trainer_version = self._version

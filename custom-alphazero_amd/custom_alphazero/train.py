@@ -9,7 +9,9 @@ two calls are parameters: `retrieve_queue() -> (states, policies, values)` and
 
 `python -m custom_alphazero.train --bench` times the training step
 (az_trainer_step, csrc/az_train.hip) on 256 boards of 6x7 at depth 4 and the
-same step in torch-ROCm autograd on the same GPU; one JSON line.
+same step in torch-ROCm autograd on the same GPU; one JSON line.  `--game
+chess` times the chess network's step (256 boards of 8x8x118 planes, 1880
+actions) the same way.
 """
 import json
 import os
@@ -77,12 +79,14 @@ def training_loop(run_id: str, retrieve_queue: Callable, update_best_model: Opti
 
 
 # ------------------------------------------------------------------ --bench
-def step_flop(n: int, height: int, width: int, depth: int, filters: int = 128) -> float:
+def step_flop(n: int, height: int, width: int, depth: int, filters: int = 128, stem_planes: int = 0) -> float:
     """FLOP of the 128 -> 128 convolutions of one step: per block two 3x3 and
     one 1x1 (19 taps), each once forward, once as data gradient and once as
-    weight gradient; the stem, the heads and the elementwise work are not counted."""
+    weight gradient; the heads and the elementwise work are not counted, and
+    neither is the stem unless `stem_planes` is given (the chess stem's 118:
+    a 3x3 convolution forward and as weight gradient; it has no data gradient)."""
     rows = n * height * width
-    return 3.0 * depth * 19 * 2.0 * rows * filters * filters
+    return 3.0 * depth * 19 * 2.0 * rows * filters * filters + 2.0 * 9 * 2.0 * rows * stem_planes * filters
 
 
 def _torch_step_time(weights, batch, depth, steps, warmup, lr, momentum, l2, eps, bn_momentum):
@@ -141,19 +145,63 @@ def _torch_step_time(weights, batch, depth, steps, warmup, lr, momentum, l2, eps
     return (time.perf_counter() - t0) / steps * 1e3
 
 
-def bench(n=256, height=6, width=7, depth=4, steps=50, warmup=5):
+def _chess_batch(rng, n):
+    """Planes shaped like chess Board.full_state (chess/board.py): per history
+    step a one-hot over 13 planes per cell and a per-board repetition plane,
+    then four castling flags and the two move counters; pi sparse over at most
+    218 of the 1880 actions."""
+    x = np.zeros((n, 8, 8, 118), np.float32)
+    for s in range(8):
+        x[..., 14 * s:14 * s + 13] = np.eye(13, dtype=np.float32)[rng.randint(0, 13, size=(n, 8, 8))]
+        x[..., 14 * s + 13] = rng.randint(0, 2, size=(n, 1, 1))
+    x[..., 112:116] = rng.randint(0, 2, size=(n, 1, 1, 4))
+    x[..., 116] = rng.randint(1, 120, size=(n, 1, 1))
+    x[..., 117] = rng.randint(0, 100, size=(n, 1, 1))
+    pi = np.zeros((n, 1880), np.float32)
+    for b in range(n):
+        moves = rng.choice(1880, size=rng.randint(1, 219), replace=False)
+        pi[b, moves] = rng.dirichlet(np.ones(len(moves)))
+    return x, pi
+
+
+def _host_copy_ms(x, repeats=20):
+    """The median time of one copy of x from pageable host memory to the device,
+    which every step makes (az_trainer_step takes host buffers)."""
+    import torch
+    dev = torch.device("cuda", 0)
+    times = []
+    for _ in range(repeats):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        torch.from_numpy(x).to(dev)
+        torch.cuda.synchronize()
+        times.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(times))
+
+
+def bench(n=256, height=6, width=7, depth=4, steps=50, warmup=5, game="connect_n"):
     from custom_alphazero import engine as az
     from custom_alphazero.model.weights import init_weights, weight_spec
-    spec = weight_spec(height, width, width, ConfigModel.filters, depth, ConfigModel.value_hidden, 4)
+    if game not in ("connect_n", "chess"):
+        raise ValueError(f"bench: game must be 'connect_n' or 'chess', got {game!r}")
+    chess = game == "chess"
+    if chess:
+        height = width = 8
+    planes, actions = (118, 1880) if chess else (4, width)
+    spec = weight_spec(height, width, actions, ConfigModel.filters, depth, ConfigModel.value_hidden, planes)
     weights = init_weights(spec, seed=0, randomize_bn=True)
     rng = np.random.RandomState(0)
-    x = np.eye(4, dtype=np.float32)[rng.randint(0, 4, size=(n, height, width))]
-    pi = rng.dirichlet(np.ones(width), size=n).astype(np.float32)
+    if chess:
+        x, pi = _chess_batch(rng, n)
+    else:
+        x = np.eye(4, dtype=np.float32)[rng.randint(0, 4, size=(n, height, width))]
+        pi = rng.dirichlet(np.ones(width), size=n).astype(np.float32)
     z = rng.randint(-1, 2, size=n).astype(np.float32)
     hyper = dict(lr=ConfigModel.minimum_learning_rate, momentum=ConfigModel.momentum,
                  l2=ConfigModel.l2_penalization_term, bn_momentum=ConfigModel.bn_momentum)
-    tr = az.Trainer(height, width, True, max_batch=n, filters=ConfigModel.filters, depth=depth,
-                    value_hidden=ConfigModel.value_hidden, bn_epsilon=ConfigModel.bn_epsilon)
+    common = dict(max_batch=n, filters=ConfigModel.filters, depth=depth, value_hidden=ConfigModel.value_hidden,
+                  bn_epsilon=ConfigModel.bn_epsilon)
+    tr = az.ChessTrainer(**common) if chess else az.Trainer(height, width, True, **common)
     tr.set_weights(weights.items())
     for _ in range(warmup):
         tr.step(x, pi, z, **hyper)
@@ -163,16 +211,26 @@ def bench(n=256, height=6, width=7, depth=4, steps=50, warmup=5):
     ms = (time.perf_counter() - t0) / steps * 1e3
     tr.close()
     torch_ms = _torch_step_time(weights, (x, pi, z), depth, steps, warmup, eps=ConfigModel.bn_epsilon, **hyper)
-    flop = step_flop(n, height, width, depth)
-    return {"bench": "train_step", "boards": n, "board": [height, width], "depth": depth, "steps": steps,
-            "warmup": warmup, "ms_per_step": round(ms, 4), "flop_per_step": flop,
-            "fp32_matrix_peak_fraction": round(flop / (ms * 1e-3) / FP32_MATRIX_PEAK, 4),
-            "torch_autograd_ms_per_step": round(torch_ms, 4)}
+    flop = step_flop(n, height, width, depth, stem_planes=planes if chess else 0)
+    rec = {"bench": "train_step", "boards": n, "board": [height, width], "depth": depth, "steps": steps,
+           "warmup": warmup, "ms_per_step": round(ms, 4), "flop_per_step": flop,
+           "fp32_matrix_peak_fraction": round(flop / (ms * 1e-3) / FP32_MATRIX_PEAK, 4),
+           "torch_autograd_ms_per_step": round(torch_ms, 4)}
+    if chess:
+        # the device step copies its batch from pageable host memory every step; the torch step above keeps
+        # its batch on the device.  flop_per_step counts the stem here.
+        copy_ms = _host_copy_ms(x)
+        rec.update({"game": "chess", "planes": planes, "actions": actions, "x_bytes": int(x.nbytes),
+                    "host_copy_ms": round(copy_ms, 4), "ms_per_step_less_copy": round(ms - copy_ms, 4)})
+    return rec
 
 
 if __name__ == "__main__":
     if "--bench" in sys.argv[1:]:
-        print(json.dumps(bench()))
+        args = sys.argv[1:]
+        game = args[args.index("--game") + 1] if "--game" in args and args.index("--game") + 1 < len(args) \
+            else "connect_n"
+        print(json.dumps(bench(game=game)))
     else:
         raise SystemExit("the serving control plane (run id, sample queue, best-model update over HTTP) is not "
                          "part of this package: call training_loop(run_id, retrieve_queue, update_best_model), "

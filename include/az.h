@@ -303,7 +303,8 @@ int az_trainer_set_weights(az_trainer* tr, const az_tensor* tensors, int n);
 int az_trainer_reset_momentum(az_trainer* tr);
 /* one tensor by name into a host buffer (Keras layout); mean/var only as AZ_TRAIN_WEIGHT */
 int az_trainer_read(az_trainer* tr, int what, const char* name, float* out, int64_t numel);
-/* x [n][H][W][4], pi [n][A], z [n] f32 host; 1 <= n <= max_batch (one board is a batch: the batch
+/* x [n][H][W][4], pi [n][A], z [n] f32 host (a chess trainer, az_chess_trainer_create in az_chess.h:
+ * x [n][8][8][118], pi [n][1880]); 1 <= n <= max_batch (one board is a batch: the batch
  * statistics run over its n*H*W rows); losses[3] = total, policy, value (of the weights before the
  * update).  AZ_E_STATE before az_trainer_set_weights. */
 int az_trainer_step(az_trainer* tr, const float* x, const float* pi, const float* z, int n,

@@ -263,6 +263,15 @@ int az_chess_tree_export(az_chess_engine* eng, int slot, double* prior, double* 
 /* HIP-event timing of the residual-tower conv launches (bench.py roofline) */
 int az_chess_timer_enable(az_chess_engine* eng, int on);
 
+/* The training step of the chess network (8x8x118 planes, 1880 actions): an az_trainer
+ * (include/az.h) that every az_trainer_* call accepts.  Reads cfg->filters, depth,
+ * value_hidden, bn_epsilon; the rest of cfg is ignored.  filters must be 128, depth 1..16,
+ * value_hidden 1..1024, bn_epsilon > 0, max_batch >= 1 and max_batch*64*128 < 2^31.
+ * az_trainer_step then takes x [n][8][8][118] (Board.full_state), pi [n][1880], z [n]; tensor
+ * names and layouts are weights.weight_spec(8, 8, 1880, 128, depth, value_hidden, 118)'s, the
+ * spec az_chess_engine_set_weights loads.  Added without a version bump: the change only adds. */
+int az_chess_trainer_create(int device, const az_chess_config* cfg, int max_batch, az_trainer** out);
+
 #ifdef __cplusplus
 }
 #endif
