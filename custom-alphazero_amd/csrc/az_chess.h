@@ -720,6 +720,66 @@ AZC_HD void state_feats(const Pos& cur, float (&feat)[6]) {
   feat[5] = (float)cur.half;
 }
 
+// LDS of full_state_block: the board's 8 history positions, their valid
+// flags, the Board.array code of every (history step, square) -- kNoCode for
+// a step that is not valid -- and the board's planes 112-117
+struct FullStateLds {
+  Pos sp[AZ_CHESS_HISTORY];
+  int sv[AZ_CHESS_HISTORY];
+  uint8_t code[AZ_CHESS_HISTORY][64];
+  float feat[6];
+};
+constexpr uint8_t kNoCode = 255;
+
+// Board.full_state of one board by one workgroup (any size >= 8; every thread
+// calls it): hist [8] oldest first and valid [8] as az_chess_encode takes
+// them -> o [8][8][118] NHWC, consecutive threads writing consecutive floats
+// (coalesced).  Each element's (pixel, plane) is computed on its own: a pixel
+// is 118 floats, so no vector width divides it.  The 512 piece codes are
+// worked out once (onehot_index reads six bitboards) and the 7552 elements
+// compare against a byte each.  Shared by encode_kernel (az_chess.hip) and
+// the replay's gather_kernel (az_replay.hip).
+__device__ inline void full_state_block(FullStateLds& s, const az_chess_pos* __restrict__ hist,
+                                        const uint8_t* __restrict__ valid, float* __restrict__ o) {
+  __syncthreads();  // the previous board's readers are done with s
+  if (threadIdx.x < AZ_CHESS_HISTORY) {
+    s.sp[threadIdx.x] = load_pos(hist[threadIdx.x]);
+    s.sv[threadIdx.x] = valid[threadIdx.x];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const Pos& cur = s.sp[AZ_CHESS_HISTORY - 1];
+    bb c = clean_castling(cur);
+    bb back_t = cur.turn ? RANK_1 : RANK_8, back_o = cur.turn ? RANK_8 : RANK_1;
+    s.feat[0] = (c & FILE_A & back_t) != 0;  // has_queenside_castling_rights(turn)
+    s.feat[1] = (c & FILE_H & back_t) != 0;  // has_kingside_castling_rights(turn)
+    s.feat[2] = (c & FILE_A & back_o) != 0;
+    s.feat[3] = (c & FILE_H & back_o) != 0;
+    s.feat[4] = (float)cur.full;
+    s.feat[5] = (float)cur.half;
+  }
+  for (int t = threadIdx.x; t < AZ_CHESS_HISTORY * 64; t += blockDim.x) {
+    const int h = t >> 6, sq = t & 63;
+    s.code[h][sq] = s.sv[h] ? (uint8_t)onehot_index(s.sp[h], sq) : kNoCode;
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < 64 * AZ_CHESS_PLANES; e += blockDim.x) {
+    int pix = e / AZ_CHESS_PLANES, k = e - pix * AZ_CHESS_PLANES;
+    int sq = (7 - (pix >> 3)) * 8 + (pix & 7);  // row 0 = rank 8 (Board.array)
+    float v;
+    if (k >= 112) {
+      v = s.feat[k - 112];
+    } else {
+      int h = k / 14, j = k - h * 14;
+      const int c = s.code[h][sq];
+      if (c == kNoCode) v = 0.f;
+      else if (j == 13) v = (float)s.sp[h].rep;
+      else v = c == j ? 1.f : 0.f;
+    }
+    o[e] = v;
+  }
+}
+
 // planes k0..k0+3 (k0 >= 64) of network-input pixel pix of a board whose
 // history is [0 x 6, start, cur] -- or [0 x 7, start-position state] for a
 // root set by reset (`initial`) -- as encode_queue_kernel writes them: planes

@@ -157,44 +157,10 @@ __global__ void __launch_bounds__(64) legal_kernel(const az_chess_pos* __restric
 __global__ void __launch_bounds__(256) encode_kernel(const az_chess_pos* __restrict__ hist,
                                                      const uint8_t* __restrict__ valid, int n,
                                                      float* __restrict__ out) {
-  __shared__ Pos sp[AZ_CHESS_HISTORY];
-  __shared__ int sv[AZ_CHESS_HISTORY];
-  __shared__ float feat[6];
-  for (int b = blockIdx.x; b < n; b += gridDim.x) {
-    __syncthreads();
-    if (threadIdx.x < AZ_CHESS_HISTORY) {
-      sp[threadIdx.x] = load_pos(hist[(size_t)b * AZ_CHESS_HISTORY + threadIdx.x]);
-      sv[threadIdx.x] = valid[(size_t)b * AZ_CHESS_HISTORY + threadIdx.x];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const Pos& cur = sp[AZ_CHESS_HISTORY - 1];
-      bb c = clean_castling(cur);
-      bb back_t = cur.turn ? RANK_1 : RANK_8, back_o = cur.turn ? RANK_8 : RANK_1;
-      feat[0] = (c & FILE_A & back_t) != 0;  // has_queenside_castling_rights(turn)
-      feat[1] = (c & FILE_H & back_t) != 0;  // has_kingside_castling_rights(turn)
-      feat[2] = (c & FILE_A & back_o) != 0;
-      feat[3] = (c & FILE_H & back_o) != 0;
-      feat[4] = (float)cur.full;
-      feat[5] = (float)cur.half;
-    }
-    __syncthreads();
-    float* o = out + (size_t)b * 64 * AZ_CHESS_PLANES;
-    for (int e = threadIdx.x; e < 64 * AZ_CHESS_PLANES; e += blockDim.x) {
-      int pix = e / AZ_CHESS_PLANES, k = e - pix * AZ_CHESS_PLANES;
-      int sq = (7 - (pix >> 3)) * 8 + (pix & 7);  // row 0 = rank 8 (Board.array)
-      float v;
-      if (k >= 112) {
-        v = feat[k - 112];
-      } else {
-        int h = k / 14, j = k - h * 14;
-        if (!sv[h]) v = 0.f;
-        else if (j == 13) v = (float)sp[h].rep;
-        else v = onehot_index(sp[h], sq) == j ? 1.f : 0.f;
-      }
-      o[e] = v;
-    }
-  }
+  __shared__ FullStateLds lds;
+  for (int b = blockIdx.x; b < n; b += gridDim.x)
+    full_state_block(lds, hist + (size_t)b * AZ_CHESS_HISTORY, valid + (size_t)b * AZ_CHESS_HISTORY,
+                     out + (size_t)b * 64 * AZ_CHESS_PLANES);
 }
 
 __global__ void play_kernel(az_chess_pos* pos, const uint16_t* __restrict__ moves, int n, int keep) {

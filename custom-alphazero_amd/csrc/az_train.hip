@@ -23,6 +23,7 @@
 #include "../../include/az.h"
 #include "../../include/az_chess.h"
 #include "az_host.h"
+#include "az_replay.h"
 #include "az_train.h"
 
 namespace az {
@@ -1209,6 +1210,127 @@ int build_trainer(az_trainer* tr) {
   return AZ_OK;
 }
 
+// The step on the batch already in tr->x, tr->pi, tr->z (n boards) on tr's stream, and the wait for
+// it: what az_trainer_step runs after its copies and az_trainer_step_replay after its gather.
+int step_on_device_batch(az_trainer* tr, int n, double lr, double momentum, double l2, double bn_momentum,
+                         float* losses) {
+  hipStream_t s = tr->stream;
+  const T::Geo& g = tr->geo;
+  const int HW = g.HW, A = g.A, hidden = g.hidden, depth = tr->depth;
+  const int rows = n * HW;
+  const float eps = (float)tr->cfg.bn_epsilon;
+  const bool chess = tr->cin == T::kChessPlanes;
+  float *w = tr->w, *gr = tr->g;
+  auto tw = [&](const char* name) { return w + tr->tensors[name].off; };
+  auto tg = [&](const char* name) { return gr + tr->tensors[name].off; };
+  auto stats = [&](const Unit& u) {
+    T::bn_stats(s, u.y, rows, u.cout, eps, tr->partial, tr->bmean + u.stat, tr->bvar + u.stat, tr->invstd + u.stat);
+  };
+  auto apply = [&](const Unit& u, const Unit* u2, bool relu, float* out) {
+    T::bn_apply(s, u.y, tr->bmean + u.stat, tr->invstd + u.stat, w + u.gamma, w + u.beta, u2 ? u2->y : nullptr,
+                u2 ? tr->bmean + u2->stat : nullptr, u2 ? tr->invstd + u2->stat : nullptr,
+                u2 ? w + u2->gamma : nullptr, u2 ? w + u2->beta : nullptr, relu, out, rows, u.cout);
+  };
+  auto bn_bwd = [&](const Unit& u, const float* gin, const float* mask_out, float* dy) {
+    T::bn_backward(s, gin, mask_out, u.y, tr->bmean + u.stat, tr->invstd + u.stat, w + u.gamma, tr->partial,
+                   gr + u.gamma, gr + u.beta, dy, rows, u.cout);
+  };
+  std::vector<Unit>& U = tr->units;
+  Unit& stem = U[0];
+  Unit& upol = U[1 + 3 * depth];
+  Unit& uval = U[2 + 3 * depth];
+
+  // ---- forward
+  if (chess)
+    T::chess_stem_forward(s, g, tr->x, w + stem.kernel, w + stem.bias, stem.y, rows);
+  else
+    T::stem_forward(s, g, tr->x, w + stem.kernel, w + stem.bias, stem.y, rows);
+  stats(stem);
+  apply(stem, nullptr, true, tr->h[0]);
+  for (int d = 0; d < depth; ++d) {
+    Unit &c1 = U[1 + 3 * d], &c2 = U[2 + 3 * d], &rs = U[3 + 3 * d];
+    T::conv_forward(s, g, 9, tr->h[d], w + c1.kernel, w + c1.bias, c1.y, rows);
+    stats(c1);
+    apply(c1, nullptr, true, tr->a1[d]);
+    T::conv_forward(s, g, 9, tr->a1[d], w + c2.kernel, w + c2.bias, c2.y, rows);
+    stats(c2);
+    T::conv_forward(s, g, 1, tr->h[d], w + rs.kernel, w + rs.bias, rs.y, rows);
+    stats(rs);
+    apply(c2, &rs, true, tr->h[d + 1]);
+  }
+  const float* top = tr->h[depth];
+  T::headconv_forward(s, top, w + upol.kernel, w + upol.bias, w + uval.kernel, w + uval.bias, upol.y, uval.y, rows);
+  stats(upol);
+  stats(uval);
+  apply(upol, nullptr, true, tr->hp);
+  apply(uval, nullptr, true, tr->hv);
+
+  // ---- heads: dense layers, losses and their gradients
+  T::HeadsArgs ha{};
+  ha.hp = tr->hp, ha.hv = tr->hv;
+  ha.wpd = tw("policy.dense.kernel"), ha.bpd = tw("policy.dense.bias");
+  ha.wv1 = tw("value.dense1.kernel"), ha.bv1 = tw("value.dense1.bias");
+  ha.wv2 = tw("value.dense2.kernel"), ha.bv2 = tw("value.dense2.bias");
+  ha.pi = tr->pi, ha.z = tr->z;
+  ha.dlogit = tr->dlogit, ha.d1 = tr->d1, ha.dpre1 = tr->dpre1, ha.dpre2 = tr->dpre2;
+  ha.ghp = tr->ghp, ha.ghv = tr->ghv, ha.lossp = tr->lossp, ha.lossv = tr->lossv;
+  if (chess)
+    T::chess_heads_forward_backward(s, g, ha, n);
+  else
+    T::heads_forward_backward(s, g, ha, n);
+  T::losses(s, w, tr->n_l2, l2, tr->lossp, tr->lossv, n, tr->sq_partial, tr->losses);
+  if (chess)
+    T::chess_policy_wgrad(s, tr->hp, tr->dlogit, tg("policy.dense.kernel"), tg("policy.dense.bias"), n);
+  else
+    T::dense_wgrad(s, tr->hp, tr->dlogit, tg("policy.dense.kernel"), tg("policy.dense.bias"), n, 2 * HW, A);
+  T::dense_wgrad(s, tr->hv, tr->dpre1, tg("value.dense1.kernel"), tg("value.dense1.bias"), n, HW, hidden);
+  T::dense_wgrad(s, tr->d1, tr->dpre2, tg("value.dense2.kernel"), tg("value.dense2.bias"), n, hidden, 1);
+
+  // ---- backward through the head convs into the tower's output
+  bn_bwd(upol, tr->ghp, tr->hp, tr->dyp);
+  bn_bwd(uval, tr->ghv, tr->hv, tr->dyv);
+  T::headconv_wgrad(s, top, tr->dyp, tr->dyv, tr->partial, gr + upol.kernel, gr + uval.kernel, rows);
+  float *gh = tr->ga, *gx = tr->gb;  // gradient of h[d + 1]; scratch
+  T::headconv_dgrad(s, tr->dyp, tr->dyv, w + upol.kernel, w + uval.kernel, gh, rows);
+  // the bias of a conv in front of a training-mode BN has an exactly zero gradient: the
+  // gradient blob's bias entries of every unit stay at the zeros they were allocated with
+
+  // ---- backward through the tower
+  for (int d = depth - 1; d >= 0; --d) {
+    Unit &c1 = U[1 + 3 * d], &c2 = U[2 + 3 * d], &rs = U[3 + 3 * d];
+    bn_bwd(c2, gh, tr->h[d + 1], tr->dy2);
+    T::conv_wgrad(s, g, 9, tr->a1[d], tr->dy2, tr->partial, gr + c2.kernel, n);
+    T::conv_dgrad(s, g, 9, tr->dy2, w + c2.kernel, nullptr, nullptr, gx, rows);  // gradient of a1
+    bn_bwd(rs, gh, tr->h[d + 1], tr->dy2);                                       // dy of the projection
+    T::conv_wgrad(s, g, 1, tr->h[d], tr->dy2, tr->partial, gr + rs.kernel, n);
+    bn_bwd(c1, gx, tr->a1[d], tr->dy1);
+    T::conv_wgrad(s, g, 9, tr->h[d], tr->dy1, tr->partial, gr + c1.kernel, n);
+    T::conv_dgrad(s, g, 9, tr->dy1, w + c1.kernel, tr->dy2, w + rs.kernel, gx, rows);  // gradient of h[d]
+    std::swap(gh, gx);
+  }
+  bn_bwd(stem, gh, tr->h[0], tr->dy1);
+  if (chess)
+    T::chess_stem_wgrad(s, g, tr->x, tr->dy1, tr->partial, gr + stem.kernel, n);
+  else
+    T::stem_wgrad(s, g, tr->x, tr->dy1, tr->partial, gr + stem.kernel, rows);
+
+  // ---- update
+  T::sgd_update(s, w, gr, tr->m, tr->n_train, tr->n_l2, (float)lr, (float)momentum, (float)l2);
+  // 1 - m: the Connect-N trainer keeps the fp32 difference it has always used (1 - 0.99f is 9.5e-7
+  // short of 0.01); the chess trainer rounds the float64 difference once.  A moving mean is one
+  // scalar a channel, m * mean + (1 - m) * mu can cancel, and with the chess test's value head
+  // (0.0035 left of terms of 0.018) the short factor alone put it 1.8e-6 from float64.
+  const float take = chess ? (float)(1.0 - bn_momentum) : 1.0f - (float)bn_momentum;
+  T::moving_update(s, w + tr->n_train, tr->bmean, tr->n_stats, (float)bn_momentum, take,
+                   (float)T::moving_variance_factor(rows));
+  AZ_HIP(hipGetLastError());
+  float host_losses[3];
+  AZ_HIP(hipMemcpyAsync(host_losses, tr->losses, sizeof(host_losses), hipMemcpyDeviceToHost, s));
+  AZ_HIP(hipStreamSynchronize(s));
+  if (losses) memcpy(losses, host_losses, sizeof(host_losses));
+  return AZ_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1347,123 +1469,29 @@ int az_trainer_step(az_trainer* tr, const float* x, const float* pi, const float
   if (!tr->has_weights) return fail_abi(AZ_E_STATE, "az_trainer_step: no weights (az_trainer_set_weights first)");
   AZ_HIP(hipSetDevice(tr->device));
   hipStream_t s = tr->stream;
-  const T::Geo& g = tr->geo;
-  const int HW = g.HW, A = g.A, hidden = g.hidden, depth = tr->depth;
-  const int rows = n * HW;
-  const float eps = (float)tr->cfg.bn_epsilon;
-  const bool chess = tr->cin == T::kChessPlanes;
-  AZ_HIP(hipMemcpyAsync(tr->x, x, (size_t)rows * tr->cin * sizeof(float), hipMemcpyHostToDevice, s));
-  AZ_HIP(hipMemcpyAsync(tr->pi, pi, (size_t)n * A * sizeof(float), hipMemcpyHostToDevice, s));
+  const size_t rows = (size_t)n * tr->geo.HW;
+  AZ_HIP(hipMemcpyAsync(tr->x, x, rows * tr->cin * sizeof(float), hipMemcpyHostToDevice, s));
+  AZ_HIP(hipMemcpyAsync(tr->pi, pi, (size_t)n * tr->geo.A * sizeof(float), hipMemcpyHostToDevice, s));
   AZ_HIP(hipMemcpyAsync(tr->z, z, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s));
-  float *w = tr->w, *gr = tr->g;
-  auto tw = [&](const char* name) { return w + tr->tensors[name].off; };
-  auto tg = [&](const char* name) { return gr + tr->tensors[name].off; };
-  auto stats = [&](const Unit& u) {
-    T::bn_stats(s, u.y, rows, u.cout, eps, tr->partial, tr->bmean + u.stat, tr->bvar + u.stat, tr->invstd + u.stat);
-  };
-  auto apply = [&](const Unit& u, const Unit* u2, bool relu, float* out) {
-    T::bn_apply(s, u.y, tr->bmean + u.stat, tr->invstd + u.stat, w + u.gamma, w + u.beta, u2 ? u2->y : nullptr,
-                u2 ? tr->bmean + u2->stat : nullptr, u2 ? tr->invstd + u2->stat : nullptr,
-                u2 ? w + u2->gamma : nullptr, u2 ? w + u2->beta : nullptr, relu, out, rows, u.cout);
-  };
-  auto bn_bwd = [&](const Unit& u, const float* gin, const float* mask_out, float* dy) {
-    T::bn_backward(s, gin, mask_out, u.y, tr->bmean + u.stat, tr->invstd + u.stat, w + u.gamma, tr->partial,
-                   gr + u.gamma, gr + u.beta, dy, rows, u.cout);
-  };
-  std::vector<Unit>& U = tr->units;
-  Unit& stem = U[0];
-  Unit& upol = U[1 + 3 * depth];
-  Unit& uval = U[2 + 3 * depth];
+  return step_on_device_batch(tr, n, lr, momentum, l2, bn_momentum, losses);
+}
 
-  // ---- forward
-  if (chess)
-    T::chess_stem_forward(s, g, tr->x, w + stem.kernel, w + stem.bias, stem.y, rows);
-  else
-    T::stem_forward(s, g, tr->x, w + stem.kernel, w + stem.bias, stem.y, rows);
-  stats(stem);
-  apply(stem, nullptr, true, tr->h[0]);
-  for (int d = 0; d < depth; ++d) {
-    Unit &c1 = U[1 + 3 * d], &c2 = U[2 + 3 * d], &rs = U[3 + 3 * d];
-    T::conv_forward(s, g, 9, tr->h[d], w + c1.kernel, w + c1.bias, c1.y, rows);
-    stats(c1);
-    apply(c1, nullptr, true, tr->a1[d]);
-    T::conv_forward(s, g, 9, tr->a1[d], w + c2.kernel, w + c2.bias, c2.y, rows);
-    stats(c2);
-    T::conv_forward(s, g, 1, tr->h[d], w + rs.kernel, w + rs.bias, rs.y, rows);
-    stats(rs);
-    apply(c2, &rs, true, tr->h[d + 1]);
-  }
-  const float* top = tr->h[depth];
-  T::headconv_forward(s, top, w + upol.kernel, w + upol.bias, w + uval.kernel, w + uval.bias, upol.y, uval.y, rows);
-  stats(upol);
-  stats(uval);
-  apply(upol, nullptr, true, tr->hp);
-  apply(uval, nullptr, true, tr->hv);
-
-  // ---- heads: dense layers, losses and their gradients
-  T::HeadsArgs ha{};
-  ha.hp = tr->hp, ha.hv = tr->hv;
-  ha.wpd = tw("policy.dense.kernel"), ha.bpd = tw("policy.dense.bias");
-  ha.wv1 = tw("value.dense1.kernel"), ha.bv1 = tw("value.dense1.bias");
-  ha.wv2 = tw("value.dense2.kernel"), ha.bv2 = tw("value.dense2.bias");
-  ha.pi = tr->pi, ha.z = tr->z;
-  ha.dlogit = tr->dlogit, ha.d1 = tr->d1, ha.dpre1 = tr->dpre1, ha.dpre2 = tr->dpre2;
-  ha.ghp = tr->ghp, ha.ghv = tr->ghv, ha.lossp = tr->lossp, ha.lossv = tr->lossv;
-  if (chess)
-    T::chess_heads_forward_backward(s, g, ha, n);
-  else
-    T::heads_forward_backward(s, g, ha, n);
-  T::losses(s, w, tr->n_l2, l2, tr->lossp, tr->lossv, n, tr->sq_partial, tr->losses);
-  if (chess)
-    T::chess_policy_wgrad(s, tr->hp, tr->dlogit, tg("policy.dense.kernel"), tg("policy.dense.bias"), n);
-  else
-    T::dense_wgrad(s, tr->hp, tr->dlogit, tg("policy.dense.kernel"), tg("policy.dense.bias"), n, 2 * HW, A);
-  T::dense_wgrad(s, tr->hv, tr->dpre1, tg("value.dense1.kernel"), tg("value.dense1.bias"), n, HW, hidden);
-  T::dense_wgrad(s, tr->d1, tr->dpre2, tg("value.dense2.kernel"), tg("value.dense2.bias"), n, hidden, 1);
-
-  // ---- backward through the head convs into the tower's output
-  bn_bwd(upol, tr->ghp, tr->hp, tr->dyp);
-  bn_bwd(uval, tr->ghv, tr->hv, tr->dyv);
-  T::headconv_wgrad(s, top, tr->dyp, tr->dyv, tr->partial, gr + upol.kernel, gr + uval.kernel, rows);
-  float *gh = tr->ga, *gx = tr->gb;  // gradient of h[d + 1]; scratch
-  T::headconv_dgrad(s, tr->dyp, tr->dyv, w + upol.kernel, w + uval.kernel, gh, rows);
-  // the bias of a conv in front of a training-mode BN has an exactly zero gradient: the
-  // gradient blob's bias entries of every unit stay at the zeros they were allocated with
-
-  // ---- backward through the tower
-  for (int d = depth - 1; d >= 0; --d) {
-    Unit &c1 = U[1 + 3 * d], &c2 = U[2 + 3 * d], &rs = U[3 + 3 * d];
-    bn_bwd(c2, gh, tr->h[d + 1], tr->dy2);
-    T::conv_wgrad(s, g, 9, tr->a1[d], tr->dy2, tr->partial, gr + c2.kernel, n);
-    T::conv_dgrad(s, g, 9, tr->dy2, w + c2.kernel, nullptr, nullptr, gx, rows);  // gradient of a1
-    bn_bwd(rs, gh, tr->h[d + 1], tr->dy2);                                       // dy of the projection
-    T::conv_wgrad(s, g, 1, tr->h[d], tr->dy2, tr->partial, gr + rs.kernel, n);
-    bn_bwd(c1, gx, tr->a1[d], tr->dy1);
-    T::conv_wgrad(s, g, 9, tr->h[d], tr->dy1, tr->partial, gr + c1.kernel, n);
-    T::conv_dgrad(s, g, 9, tr->dy1, w + c1.kernel, tr->dy2, w + rs.kernel, gx, rows);  // gradient of h[d]
-    std::swap(gh, gx);
-  }
-  bn_bwd(stem, gh, tr->h[0], tr->dy1);
-  if (chess)
-    T::chess_stem_wgrad(s, g, tr->x, tr->dy1, tr->partial, gr + stem.kernel, n);
-  else
-    T::stem_wgrad(s, g, tr->x, tr->dy1, tr->partial, gr + stem.kernel, rows);
-
-  // ---- update
-  T::sgd_update(s, w, gr, tr->m, tr->n_train, tr->n_l2, (float)lr, (float)momentum, (float)l2);
-  // 1 - m: the Connect-N trainer keeps the fp32 difference it has always used (1 - 0.99f is 9.5e-7
-  // short of 0.01); the chess trainer rounds the float64 difference once.  A moving mean is one
-  // scalar a channel, m * mean + (1 - m) * mu can cancel, and with the chess test's value head
-  // (0.0035 left of terms of 0.018) the short factor alone put it 1.8e-6 from float64.
-  const float take = chess ? (float)(1.0 - bn_momentum) : 1.0f - (float)bn_momentum;
-  T::moving_update(s, w + tr->n_train, tr->bmean, tr->n_stats, (float)bn_momentum, take,
-                   (float)T::moving_variance_factor(rows));
-  AZ_HIP(hipGetLastError());
-  float host_losses[3];
-  AZ_HIP(hipMemcpyAsync(host_losses, tr->losses, sizeof(host_losses), hipMemcpyDeviceToHost, s));
-  AZ_HIP(hipStreamSynchronize(s));
-  if (losses) memcpy(losses, host_losses, sizeof(host_losses));
-  return AZ_OK;
+int az_trainer_step_replay(az_trainer* tr, az_chess_replay* rp, const int64_t* idx, int n, double lr,
+                           double momentum, double l2, double bn_momentum, float* losses) {
+  if (!tr || !rp || !idx) return fail_abi(AZ_E_INVALID, "az_trainer_step_replay: null argument");
+  if (tr->cin != T::kChessPlanes)
+    return fail_abi(AZ_E_INVALID, "az_trainer_step_replay: the trainer is not the chess network's "
+                                  "(az_chess_trainer_create)");
+  if (n < 1 || n > tr->max_batch)
+    return fail_abi(AZ_E_INVALID, "az_trainer_step_replay: n must be 1..max_batch");
+  if (!tr->has_weights)
+    return fail_abi(AZ_E_STATE, "az_trainer_step_replay: no weights (az_trainer_set_weights first)");
+  if (az::replay::device_of(rp) != tr->device)
+    return fail_abi(AZ_E_INVALID, "az_trainer_step_replay: the replay is on another device than the trainer");
+  AZ_HIP(hipSetDevice(tr->device));
+  // the batch goes from the window straight into the step's own input buffers
+  AZ_TRY(az::replay::gather_on(rp, idx, n, tr->stream, tr->x, tr->pi, tr->z, "az_trainer_step_replay"));
+  return step_on_device_batch(tr, n, lr, momentum, l2, bn_momentum, losses);
 }
 
 }  // extern "C"

@@ -112,6 +112,8 @@ EXPORTED = (
     "az_chess_tree_reset",
     "az_chess_tree_release", "az_chess_tree_search", "az_chess_tree_search_noise", "az_chess_tree_play", "az_chess_tree_info",
     "az_chess_tree_export", "az_chess_trainer_create",
+    "az_chess_replay_create", "az_chess_replay_destroy", "az_chess_replay_push", "az_chess_replay_size",
+    "az_chess_replay_clear", "az_chess_replay_gather", "az_trainer_step_replay",
 )
 
 _lib = None
@@ -199,6 +201,14 @@ def load_library():
         "az_chess_tree_export": (ctypes.c_int, [P, ctypes.c_int, P, P, P, P, P, P, P]),
         "az_chess_trainer_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ChessConfig), ctypes.c_int,
                                                    ctypes.POINTER(P)]),
+        "az_chess_replay_create": (ctypes.c_int, [ctypes.c_int, I64, ctypes.POINTER(P)]),
+        "az_chess_replay_destroy": (ctypes.c_int, [P]),
+        "az_chess_replay_push": (ctypes.c_int, [P, P, P, P, P, P, P, I64]),
+        "az_chess_replay_size": (ctypes.c_int, [P, ctypes.POINTER(I64), ctypes.POINTER(I64)]),
+        "az_chess_replay_clear": (ctypes.c_int, [P]),
+        "az_chess_replay_gather": (ctypes.c_int, [P, P, ctypes.c_int, P, P, P]),
+        "az_trainer_step_replay": (ctypes.c_int, [P, P, P, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                                  ctypes.c_double, ctypes.c_double, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -588,6 +598,17 @@ class Trainer:
                                        float(l2), float(bn_momentum), _ptr(losses)))
         return float(losses[0]), float(losses[1]), float(losses[2])
 
+    def step_replay(self, replay, idx, lr, momentum=0.9, l2=1e-4, bn_momentum=0.99):
+        """step on the samples idx of a ChessReplay window, gathered on the
+        device into the step's own input buffers (az_trainer_step_replay):
+        returns what step(*replay.gather(idx), ...) returns, bit for bit.
+        The chess trainer's; on this Connect-N class the library refuses."""
+        idx = np.ascontiguousarray(idx, np.int64).reshape(-1)
+        losses = np.zeros(3, np.float32)
+        _check(self._L.az_trainer_step_replay(self._h, replay._h, _ptr(idx), len(idx), float(lr),
+                                              float(momentum), float(l2), float(bn_momentum), _ptr(losses)))
+        return float(losses[0]), float(losses[1]), float(losses[2])
+
 
 class ChessTrainer(Trainer):
     """The trainer of the chess network (az_chess_trainer_create): the
@@ -609,6 +630,116 @@ class ChessTrainer(Trainer):
         _check(L.az_chess_trainer_create(int(device), ctypes.byref(cfg), self.max_batch, ctypes.byref(handle)))
         self._h = handle
         self._L = L
+
+
+def chess_replay_records(results, start=None):
+    """The samples of finished chess games as ChessReplay.push takes them, from
+    the dict of ChessEngine.selfplay_results() or selfplay_drain(): every ply
+    of every game, in game order, with the history self_play.play_chess gives
+    it -- [0 x 7, pos] for a game's first ply, [0 x 6, start, pos] afterwards
+    (start: the start position's record, default Board()'s) -- its sparse
+    policy row, and z = self_play.alternating_rewards(result, T) as float32.
+    Host bookkeeping only: no device work."""
+    from custom_alphazero.chess import kernels as K
+    from custom_alphazero.self_play import alternating_rewards
+    if start is None:
+        from custom_alphazero.chess.board import Board as ChessBoard
+        start = ChessBoard()._pos
+    lengths = np.asarray(results["lengths"]).astype(np.int64)
+    hist, valid, z, rows = [], [], [], []
+    for g, T in enumerate(lengths):
+        T = int(T)
+        h = np.zeros((T, K.HISTORY), K.POS_DTYPE)
+        v = np.zeros((T, K.HISTORY), np.uint8)
+        h[:, 7], v[:, 7] = results["positions"][g, :T], 1
+        h[1:, 6], v[1:, 6] = start, 1
+        hist.append(h)
+        valid.append(v)
+        z.append(np.asarray(alternating_rewards(int(results["results"][g]), T), np.float64).astype(np.float32))
+        rows.append((np.full(T, g), np.arange(T)))
+    gi = np.concatenate([r[0] for r in rows]) if rows else np.zeros(0, np.int64)
+    ti = np.concatenate([r[1] for r in rows]) if rows else np.zeros(0, np.int64)
+    M = ChessEngine.MAX_MOVES
+    return dict(
+        hist=np.concatenate(hist) if hist else np.zeros((0, K.HISTORY), K.POS_DTYPE),
+        valid=np.concatenate(valid) if valid else np.zeros((0, K.HISTORY), np.uint8),
+        policy_n=np.ascontiguousarray(np.asarray(results["policy_n"])[gi, ti], np.int32).reshape(-1),
+        policy_actions=np.ascontiguousarray(np.asarray(results["policy_actions"])[gi, ti], np.int16).reshape(-1, M),
+        policy_probs=np.ascontiguousarray(np.asarray(results["policy_probs"])[gi, ti], np.float64).reshape(-1, M),
+        z=np.concatenate(z) if z else np.zeros(0, np.float32))
+
+
+class ChessReplay:
+    """The chess replay window on the device (az_chess_replay_*,
+    csrc/az_replay.hip): a ring of the newest `capacity` samples in the compact
+    form self-play produces (8 history positions, the sparse policy, the value;
+    about 3.2 KB a sample), from which ChessTrainer.step_replay trains without
+    a dense state ever being built on the host.  Index 0 is the oldest sample
+    held, len(replay) - 1 the newest: the row order of train.training_loop's
+    host window, so the same np.random.choice indices name the same samples.
+    One thread drives a replay and the trainer stepping from it."""
+
+    KEYS = ("hist", "valid", "policy_n", "policy_actions", "policy_probs", "z")
+
+    def __init__(self, capacity, device=0):
+        L = load_library()
+        handle = ctypes.c_void_p()
+        _check(L.az_chess_replay_create(int(device), int(capacity), ctypes.byref(handle)))
+        self._h, self._L = handle, L
+        self.capacity = int(capacity)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.az_chess_replay_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # pragma: no cover - interpreter teardown
+            pass
+
+    def __len__(self):
+        size = ctypes.c_int64(0)
+        _check(self._L.az_chess_replay_size(self._h, ctypes.byref(size), None))
+        return int(size.value)
+
+    def push(self, hist, valid, policy_n, policy_actions, policy_probs, z):
+        """Append n samples in order: hist [n, 8] positions (POS_DTYPE) oldest
+        first and valid [n, 8] as chess.kernels.encode takes them, policy_n [n],
+        policy_actions [n, 256], policy_probs [n, 256] float64, z [n].  A row
+        with policy_n outside 0..256, a used action outside 0..1879 or an
+        action used twice raises AzError and leaves the window unchanged."""
+        from custom_alphazero.chess.kernels import HISTORY, POS_DTYPE
+        M = ChessEngine.MAX_MOVES
+        pn = np.ascontiguousarray(policy_n, np.int32).reshape(-1)
+        n = len(pn)
+        h = np.ascontiguousarray(hist, POS_DTYPE).reshape(n, HISTORY)
+        v = np.ascontiguousarray(valid, np.uint8).reshape(n, HISTORY)
+        pa = np.ascontiguousarray(policy_actions, np.int16).reshape(n, M)
+        pp = np.ascontiguousarray(policy_probs, np.float64).reshape(n, M)
+        zz = np.ascontiguousarray(z, np.float32).reshape(n)
+        _check(self._L.az_chess_replay_push(self._h, _ptr(h), _ptr(v), _ptr(pn), _ptr(pa), _ptr(pp), _ptr(zz), n))
+
+    def push_games(self, results, start=None):
+        """Push every ply of the finished games in `results` (the dict of
+        ChessEngine.selfplay_results() or selfplay_drain()), in game order, as
+        self_play.play_chess builds its samples (chess_replay_records)."""
+        self.push(**chess_replay_records(results, start))
+
+    def gather(self, idx):
+        """-> (x [n, 8, 8, 118], pi [n, 1880], z [n]) float32: the samples idx in
+        the dense form Trainer.step takes (az_chess_replay_gather)."""
+        idx = np.ascontiguousarray(idx, np.int64).reshape(-1)
+        n = len(idx)
+        x = np.zeros((n, 8, 8, 118), np.float32)
+        pi = np.zeros((n, ChessEngine.ACTIONS), np.float32)
+        z = np.zeros(n, np.float32)
+        _check(self._L.az_chess_replay_gather(self._h, _ptr(idx), n, _ptr(x), _ptr(pi), _ptr(z)))
+        return x, pi, z
+
+    def clear(self):
+        _check(self._L.az_chess_replay_clear(self._h))
 
 
 class ChessEngine:

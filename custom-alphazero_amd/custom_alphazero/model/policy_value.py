@@ -192,6 +192,18 @@ class PolicyValueModel:
         self._trainer_ahead = True
         return total
 
+    def train_on_replay(self, replay, idx):
+        """train_on_batch on the samples idx of an engine.ChessReplay window:
+        the batch is gathered on the device (ChessTrainer.step_replay), the
+        step and the returned loss are train_on_batch's on replay.gather(idx)."""
+        tr = self.trainer()
+        total, _, _ = tr.step_replay(replay, idx, self.learning_rate, ConfigModel.momentum,
+                                     ConfigModel.l2_penalization_term, ConfigModel.bn_momentum)
+        self._version += 1
+        self._trainer_version = self._version
+        self._trainer_ahead = True
+        return total
+
     # ------------------------------------------------------------ persistence
     def save_with_meta(self, path):
         os.makedirs(path, exist_ok=True)

@@ -42,6 +42,25 @@ def train(model, inputs: np.ndarray, labels: List[np.ndarray], batch_size: int, 
     return loss
 
 
+def train_replay(model, replay, idx: np.ndarray, batch_size: int, epochs: int) -> float:
+    """train() on the samples idx of an engine.ChessReplay window, batch by batch through
+    PolicyValueModel.train_on_replay: the same slices, loss weighting, steps and
+    learning-rate schedule; no dense batch is built on the host."""
+    idx = np.ascontiguousarray(idx, np.int64).reshape(-1)
+    n = int(idx.shape[0])
+    batches = int(math.ceil(n / batch_size))
+    loss = float("nan")
+    for _ in range(epochs):
+        weighted = 0.0
+        for b in range(batches):
+            sl = slice(b * batch_size, min(n, (b + 1) * batch_size))
+            weighted += model.train_on_replay(replay, idx[sl]) * (sl.stop - sl.start)
+        loss = weighted / n
+    model.steps += epochs * batches
+    model.update_learning_rate(scheduled_learning_rate(model.steps))
+    return loss
+
+
 def _run_path(run_id: str, *parts) -> str:
     return os.path.join(ConfigPath.results_dir, ConfigGeneral.game, run_id, *parts)
 
@@ -55,17 +74,23 @@ def _write_scalars(directory: str, step: int, **scalars):
 
 def train_and_report(run_id: str, last_model, states_batch: np.ndarray, policies_batch: np.ndarray,
                      values_batch: np.ndarray, training_iteration: int,
-                     evaluation_iteration: int) -> Tuple[bool, bool]:
+                     evaluation_iteration: int, replay=None) -> Tuple[bool, bool]:
     """One training iteration: train on the batch, checkpoint every
     model_checkpoint_frequency iterations, and every model_evaluation_frequency
     iterations play the arena against the best model so far and save the
-    winner as the new best.  Returns (is_evaluated, is_updated)."""
+    winner as the new best.  Returns (is_evaluated, is_updated).  With `replay`
+    (an engine.ChessReplay) the batch is the window's samples states_batch, an
+    index array, and policies_batch / values_batch are ignored (train_replay)."""
     from custom_alphazero.evaluation.evaluate import evaluate_two_models
     from custom_alphazero.utils import best_saved_model
 
     board = _run_path(run_id, ConfigPath.tensorboard_dir)
-    loss = train(last_model, states_batch, [policies_batch, values_batch],
-                 epochs=ConfigModel.training_epochs, batch_size=ConfigModel.batch_size)
+    if replay is not None:
+        loss = train_replay(last_model, replay, states_batch, epochs=ConfigModel.training_epochs,
+                            batch_size=ConfigModel.batch_size)
+    else:
+        loss = train(last_model, states_batch, [policies_batch, values_batch],
+                     epochs=ConfigModel.training_epochs, batch_size=ConfigModel.batch_size)
     if (training_iteration + 1) % ConfigServing.model_checkpoint_frequency == 0:
         last_model.save_with_meta(_run_path(run_id, ConfigPath.training_dir))
     _write_scalars(board, training_iteration, **{"loss": loss, "steps": last_model.steps,

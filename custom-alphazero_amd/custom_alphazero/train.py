@@ -11,7 +11,8 @@ two calls are parameters: `retrieve_queue() -> (states, policies, values)` and
 (az_trainer_step, csrc/az_train.hip) on 256 boards of 6x7 at depth 4 and the
 same step in torch-ROCm autograd on the same GPU; one JSON line.  `--game
 chess` times the chess network's step (256 boards of 8x8x118 planes, 1880
-actions) the same way.
+actions) the same way, and the same step from a device replay window
+(Trainer.step_replay: ms_per_step_replay).
 """
 import json
 import os
@@ -50,13 +51,44 @@ def last_saved_model(run_id: str):
     return init_model()
 
 
+def _replay_loop(run_id, retrieve_queue, update_best_model, max_iterations, last_model, replay):
+    """training_loop with the window on the device: the same iterations, the same
+    np.random.choice draw over the same row order, no dense state on the host."""
+    from custom_alphazero.model.tensorflow.train import train_and_report
+
+    training_iteration, evaluation_iteration = 0, 0
+    while max_iterations is None or training_iteration < max_iterations:
+        records = retrieve_queue()
+        if records:
+            replay.push(**{k: records[k] for k in replay.KEYS})
+        if len(replay) >= ConfigServing.minimum_training_size:
+            idx = np.random.choice(len(replay), ConfigModel.batch_size, replace=False)
+            is_evaluated, is_updated = train_and_report(run_id, last_model, idx, None, None, training_iteration,
+                                                        evaluation_iteration, replay=replay)
+            if is_updated and update_best_model is not None:
+                update_best_model()
+            if is_evaluated:
+                evaluation_iteration += 1
+            training_iteration += 1
+            if max_iterations is not None and training_iteration >= max_iterations:
+                break
+        time.sleep(ConfigServing.training_loop_sleep_time)
+    return last_model
+
+
 def training_loop(run_id: str, retrieve_queue: Callable, update_best_model: Optional[Callable] = None,
-                  max_iterations: Optional[int] = None, model=None):
+                  max_iterations: Optional[int] = None, model=None, replay=None):
     """Runs until max_iterations training iterations are done (None: for ever).
-    Returns the model it trained."""
+    Returns the model it trained.  With `replay` (an engine.ChessReplay the
+    caller sized to ConfigServing.samples_queue_size) the window lives on the
+    device in compact form: retrieve_queue() then returns a dict with the keys
+    of ChessReplay.push (engine.chess_replay_records makes one from self-play
+    results), or a falsy value when the queue is empty."""
     from custom_alphazero.model.tensorflow.train import train_and_report
 
     last_model = model if model is not None else last_saved_model(run_id)
+    if replay is not None:
+        return _replay_loop(run_id, retrieve_queue, update_best_model, max_iterations, last_model, replay)
     states = np.empty((0, *last_model.input_dim))
     policies = np.empty((0, last_model.action_space))
     values = np.empty(0)
@@ -145,23 +177,38 @@ def _torch_step_time(weights, batch, depth, steps, warmup, lr, momentum, l2, eps
     return (time.perf_counter() - t0) / steps * 1e3
 
 
-def _chess_batch(rng, n):
-    """Planes shaped like chess Board.full_state (chess/board.py): per history
-    step a one-hot over 13 planes per cell and a per-board repetition plane,
-    then four castling flags and the two move counters; pi sparse over at most
-    218 of the 1880 actions."""
-    x = np.zeros((n, 8, 8, 118), np.float32)
-    for s in range(8):
-        x[..., 14 * s:14 * s + 13] = np.eye(13, dtype=np.float32)[rng.randint(0, 13, size=(n, 8, 8))]
-        x[..., 14 * s + 13] = rng.randint(0, 2, size=(n, 1, 1))
-    x[..., 112:116] = rng.randint(0, 2, size=(n, 1, 1, 4))
-    x[..., 116] = rng.randint(1, 120, size=(n, 1, 1))
-    x[..., 117] = rng.randint(0, 100, size=(n, 1, 1))
-    pi = np.zeros((n, 1880), np.float32)
+def _chess_records(rng, n):
+    """A chess batch as compact replay records (the keys of engine.ChessReplay.push),
+    whose dense form is shaped like Board.full_state (chess/board.py): per
+    history step a random piece code per square, as az_chess_pos bitboards, and
+    a repetition flag; random castling rights and move counters; the policy
+    sparse over at most 218 of the 1880 actions, float64.  Every history entry
+    is valid."""
+    from custom_alphazero.chess import kernels as K
+    code = rng.randint(0, 13, size=(n, 8, 64))  # Board.array codes: 0 empty, 1..6 white P..K, 7..12 black K..P
+    hist = np.zeros((n, 8), K.POS_DTYPE)
+    bit = np.uint64(1) << np.arange(64, dtype=np.uint64)
+    for t in range(6):
+        hist["pieces"][..., t] = (((code == t + 1) | (code == 12 - t)) * bit).sum(axis=-1, dtype=np.uint64)
+    hist["occupied_co"][..., 1] = (((code >= 1) & (code <= 6)) * bit).sum(axis=-1, dtype=np.uint64)
+    hist["occupied_co"][..., 0] = ((code >= 7) * bit).sum(axis=-1, dtype=np.uint64)
+    corners = np.array([1 << 0, 1 << 7, 1 << 56, 1 << 63], np.uint64)
+    hist["castling_rights"] = (rng.randint(0, 2, size=(n, 8, 4)) * corners).sum(axis=-1, dtype=np.uint64)
+    hist["ep_square"] = -1
+    hist["turn"] = rng.randint(0, 2, size=(n, 8))
+    hist["repetition"] = rng.randint(0, 2, size=(n, 8))
+    hist["fullmove_number"] = rng.randint(1, 120, size=(n, 8))
+    hist["halfmove_clock"] = rng.randint(0, 100, size=(n, 8))
+    policy_n = np.zeros(n, np.int32)
+    actions = np.zeros((n, K.MAX_MOVES), np.int16)
+    probs = np.zeros((n, K.MAX_MOVES), np.float64)
     for b in range(n):
-        moves = rng.choice(1880, size=rng.randint(1, 219), replace=False)
-        pi[b, moves] = rng.dirichlet(np.ones(len(moves)))
-    return x, pi
+        k = rng.randint(1, 219)
+        policy_n[b] = k
+        actions[b, :k] = rng.choice(K.ACTIONS, size=k, replace=False)
+        probs[b, :k] = rng.dirichlet(np.ones(k))
+    return dict(hist=hist, valid=np.ones((n, 8), np.uint8), policy_n=policy_n, policy_actions=actions,
+                policy_probs=probs, z=rng.randint(-1, 2, size=n).astype(np.float32))
 
 
 def _host_copy_ms(x, repeats=20):
@@ -191,12 +238,17 @@ def bench(n=256, height=6, width=7, depth=4, steps=50, warmup=5, game="connect_n
     spec = weight_spec(height, width, actions, ConfigModel.filters, depth, ConfigModel.value_hidden, planes)
     weights = init_weights(spec, seed=0, randomize_bn=True)
     rng = np.random.RandomState(0)
+    replay = None
     if chess:
-        x, pi = _chess_batch(rng, n)
+        # the batch starts as compact records in a device replay window (the step_replay leg
+        # below); every other leg takes the dense arrays the window gathers from them
+        replay = az.ChessReplay(n)
+        replay.push(**_chess_records(rng, n))
+        x, pi, z = replay.gather(np.arange(n))
     else:
         x = np.eye(4, dtype=np.float32)[rng.randint(0, 4, size=(n, height, width))]
         pi = rng.dirichlet(np.ones(width), size=n).astype(np.float32)
-    z = rng.randint(-1, 2, size=n).astype(np.float32)
+        z = rng.randint(-1, 2, size=n).astype(np.float32)
     hyper = dict(lr=ConfigModel.minimum_learning_rate, momentum=ConfigModel.momentum,
                  l2=ConfigModel.l2_penalization_term, bn_momentum=ConfigModel.bn_momentum)
     common = dict(max_batch=n, filters=ConfigModel.filters, depth=depth, value_hidden=ConfigModel.value_hidden,
@@ -209,6 +261,15 @@ def bench(n=256, height=6, width=7, depth=4, steps=50, warmup=5, game="connect_n
     for _ in range(steps):
         tr.step(x, pi, z, **hyper)
     ms = (time.perf_counter() - t0) / steps * 1e3
+    if chess:
+        idx = np.arange(n)
+        for _ in range(warmup):
+            tr.step_replay(replay, idx, **hyper)
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            tr.step_replay(replay, idx, **hyper)
+        replay_ms = (time.perf_counter() - t0) / steps * 1e3
+        replay.close()
     tr.close()
     torch_ms = _torch_step_time(weights, (x, pi, z), depth, steps, warmup, eps=ConfigModel.bn_epsilon, **hyper)
     flop = step_flop(n, height, width, depth, stem_planes=planes if chess else 0)
@@ -218,10 +279,13 @@ def bench(n=256, height=6, width=7, depth=4, steps=50, warmup=5, game="connect_n
            "torch_autograd_ms_per_step": round(torch_ms, 4)}
     if chess:
         # the device step copies its batch from pageable host memory every step; the torch step above keeps
-        # its batch on the device.  flop_per_step counts the stem here.
+        # its batch on the device, and ms_per_step_replay is the step from the device replay window
+        # (Trainer.step_replay on the same boards: no dense batch on the host).  flop_per_step counts
+        # the stem here.
         copy_ms = _host_copy_ms(x)
         rec.update({"game": "chess", "planes": planes, "actions": actions, "x_bytes": int(x.nbytes),
-                    "host_copy_ms": round(copy_ms, 4), "ms_per_step_less_copy": round(ms - copy_ms, 4)})
+                    "host_copy_ms": round(copy_ms, 4), "ms_per_step_less_copy": round(ms - copy_ms, 4),
+                    "ms_per_step_replay": round(replay_ms, 4)})
     return rec
 
 

@@ -272,6 +272,60 @@ int az_chess_timer_enable(az_chess_engine* eng, int on);
  * spec az_chess_engine_set_weights loads.  Added without a version bump: the change only adds. */
 int az_chess_trainer_create(int device, const az_chess_config* cfg, int max_batch, az_trainer** out);
 
+/* ------------------------------------------------------------ replay window
+ * The chess replay window on the device: the samples the training loop draws
+ * its batches from (the reference's local_*_queue arrays, train.py:16-40), held
+ * as self-play hands them over -- each sample the board's 8 history positions
+ * and their valid flags (az_chess_encode's form), the MCTS.play policy sparsely
+ * (az_chess_selfplay_results' policy_n / policy_actions / policy_probs row) and
+ * the value: about 3.2 KB against 45 KB in dense form.  Storage is a structure
+ * of arrays: hist [cap][8] az_chess_pos, valid [cap][8] u8, policy_n [cap] i32,
+ * policy_actions [cap][256] i16, policy_probs [cap][256] f64, z [cap] f32.  One
+ * kernel gathers a batch by index, encodes the planes and scatters the policy
+ * to dense rows.  Every call is synchronous.  One thread drives a replay and the
+ * trainer that steps from it: no call on either runs beside another.  Added
+ * without a version bump: the change only adds. */
+typedef struct az_chess_replay az_chess_replay;
+
+/* capacity >= 1 samples on `device`. */
+int az_chess_replay_create(int device, int64_t capacity, az_chess_replay** out);
+int az_chess_replay_destroy(az_chess_replay* rp);
+/* Appends n samples, in order, from host buffers: hist [n][8] oldest first and
+ * valid [n][8] as az_chess_encode takes them, policy_n [n], policy_actions
+ * [n][AZ_CHESS_MAX_MOVES], policy_probs [n][AZ_CHESS_MAX_MOVES] f64 (entries
+ * past policy_n are ignored), z [n].  The window is a ring that keeps the newest
+ * `capacity` samples; a push of n > capacity keeps its last `capacity`.
+ * Checked on the host before anything is copied: 0 <= policy_n <= 256, every
+ * used action in 0..1879, and no action twice in a row of the policy (the
+ * host's dense assignment is last-wins, a parallel scatter is not).  A violation
+ * is AZ_E_INVALID and leaves the window as it was. */
+int az_chess_replay_push(az_chess_replay* rp, const az_chess_pos* hist, const uint8_t* valid,
+                         const int32_t* policy_n, const int16_t* policy_actions, const double* policy_probs,
+                         const float* z, int64_t n);
+/* Samples held, and the capacity; either pointer may be NULL. */
+int az_chess_replay_size(az_chess_replay* rp, int64_t* size, int64_t* capacity);
+/* Empties the window: the next push starts at index 0. */
+int az_chess_replay_clear(az_chess_replay* rp);
+/* The samples idx [n] in dense form, to host buffers: x [n][8][8][118]
+ * (Board.full_state, bitwise az_chess_encode's), pi [n][1880] f32 (zeros, then
+ * pi[action] = (float)prob: round to nearest, numpy's astype(float32)), z [n].
+ * Any output may be NULL.  Index 0 is the oldest sample held and size - 1 the
+ * newest: the row order of the reference's window np.vstack(...)[-size:], so the
+ * same np.random.choice indices name the same samples.  Indices may repeat and
+ * come in any order.  AZ_E_INVALID for an index outside 0..size-1, AZ_E_STATE on
+ * an empty window. */
+int az_chess_replay_gather(az_chess_replay* rp, const int64_t* idx, int n, float* x, float* pi, float* z);
+/* az_trainer_step (include/az.h) on the samples idx [n] of the window, for a
+ * trainer made by az_chess_trainer_create: the batch is gathered on the device
+ * straight into the step's input buffers, on the trainer's stream, and no dense
+ * state crosses the host.  The step itself, its preconditions and its results
+ * are az_trainer_step's on az_chess_replay_gather's arrays, bit for bit.
+ * AZ_E_INVALID for a Connect-N trainer, a replay on another device than the
+ * trainer, n outside 1..max_batch or an index outside the window; AZ_E_STATE
+ * before az_trainer_set_weights or on an empty window.  Waits for the step. */
+int az_trainer_step_replay(az_trainer* tr, az_chess_replay* rp, const int64_t* idx, int n, double lr,
+                           double momentum, double l2, double bn_momentum, float* losses);
+
 #ifdef __cplusplus
 }
 #endif
