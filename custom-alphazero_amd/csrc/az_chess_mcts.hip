@@ -164,7 +164,6 @@ struct CPlayOut {
   double* pol_p = nullptr;           // [slots][AZ_CHESS_MAX_MOVES]
 };
 
-constexpr int kMtN = 624;
 constexpr int kStemFirstChunk = 2;  // input chunks of 32 planes the self-play stem skips
 
 __device__ __forceinline__ Edge* arena(const CCfg& g, const CTree& t, int s, int h) {
@@ -172,73 +171,6 @@ __device__ __forceinline__ Edge* arena(const CCfg& g, const CTree& t, int s, int
 }
 __device__ __forceinline__ void flag(const CTree& t, unsigned long long f) {
   atomicOr(t.stats + az::kStatErrors, f);
-}
-
-// MT19937 per slot, word-major (az_tree.hip layout)
-__device__ void mt_seed(const CTree& t, int s, uint32_t seed) {
-  const int slots = t.mt_stride;
-  uint32_t prev = seed;
-  t.mt[s] = seed;
-  for (int i = 1; i < kMtN; ++i) {
-    prev = 1812433253u * (prev ^ (prev >> 30)) + (uint32_t)i;
-    t.mt[(size_t)i * slots + s] = prev;
-  }
-  t.mt[(size_t)kMtN * slots + s] = kMtN;
-}
-__device__ uint32_t mt_next(const CTree& t, int s) {
-  const int slots = t.mt_stride;
-  uint32_t* m = t.mt;
-  uint32_t pos = m[(size_t)kMtN * slots + s];
-  if (pos >= (uint32_t)kMtN) {
-    for (int i = 0; i < kMtN; ++i) {
-      const uint32_t y = (m[(size_t)i * slots + s] & 0x80000000u) |
-                         (m[(size_t)((i + 1) % kMtN) * slots + s] & 0x7fffffffu);
-      m[(size_t)i * slots + s] =
-          m[(size_t)((i + 397) % kMtN) * slots + s] ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
-    }
-    pos = 0;
-  }
-  const uint32_t y = m[(size_t)pos * slots + s];
-  m[(size_t)kMtN * slots + s] = pos + 1;
-  return az::mt_temper(y);
-}
-__device__ double mt_uniform(const CTree& t, int s) {
-  const uint32_t a = mt_next(t, s) >> 5;
-  const uint32_t b = mt_next(t, s) >> 6;
-  return ((double)a * 67108864.0 + (double)b) / 9007199254740992.0;
-}
-
-// numpy pairwise add.reduce (identity 0 + pairwise_sum, blocks of 128, 8
-// accumulators) for n <= 256 (at most two levels of splitting)
-template <typename T>
-__device__ T pw_block(const T* a, int n) {
-  if (n < 8) {
-    T r = (T)0;
-    for (int i = 0; i < n; ++i) r += a[i];
-    return r;
-  }
-  T r[8];
-  for (int j = 0; j < 8; ++j) r[j] = a[j];
-  int i = 8;
-  for (; i < n - (n % 8); i += 8)
-    for (int j = 0; j < 8; ++j) r[j] += a[i + j];
-  T res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-  for (; i < n; ++i) res += a[i];
-  return res;
-}
-template <typename T>
-__device__ T pw_136(const T* a, int n) {
-  if (n <= 128) return pw_block(a, n);
-  int n2 = n / 2;
-  n2 -= n2 % 8;
-  return pw_block(a, n2) + pw_block(a + n2, n - n2);
-}
-template <typename T>
-__device__ T pairwise(const T* a, int n) {
-  if (n <= 128) return pw_block(a, n);
-  int n2 = n / 2;
-  n2 -= n2 % 8;
-  return pw_136(a, n2) + pw_136(a + n2, n - n2);
 }
 
 // MCTS.backup (mcts.py:163-168): from the leaf's parent edge up, N + 1 and
@@ -268,7 +200,7 @@ __device__ void slot_reset(const CCfg& g, const CTree& t, const CSamples& smp, i
   t.path_len[s] = 0;
   t.slot_exp[s] = 0;
   t.game_id[s] = gid;
-  mt_seed(t, s, smp.base_seed + (uint32_t)gid);
+  az::mt_seed({t.mt + s, (size_t)t.mt_stride}, smp.base_seed + (uint32_t)gid);
 }
 
 // synthetic evaluator (oracle/chess_oracle.c orc_chess_synth): dyadic priors
@@ -328,9 +260,6 @@ __global__ void tree_release_kernel(CTree t, int n, const int32_t* slots) {
 __device__ __forceinline__ uint64_t key_hash(const Pos& q, int initial) {
   return az::splitmix64(pos_hash(q, initial) ^ ((uint64_t)(uint32_t)q.turn << 8) ^ ((uint64_t)(uint32_t)q.rep << 16));
 }
-__device__ __forceinline__ uint32_t key_bucket(const ChessCache& c, uint64_t h) {
-  return (uint32_t)h & c.mask & ~(uint32_t)(az::kCacheBucket - 1);
-}
 __device__ __forceinline__ bool same_key(const ChessKey* a, const az_chess_pos& pos, int initial) {
   const uint4* x = reinterpret_cast<const uint4*>(a);
   const uint4* y = reinterpret_cast<const uint4*>(&pos);
@@ -354,7 +283,7 @@ __device__ bool cache_probe_wave(const CTree& t, const ChessCache& c, int s, int
   int idx = -1;
   if (lane == 0) {
     const uint32_t gen = (uint32_t)__hip_atomic_load(c.ctl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const uint32_t fp = az::cache_fp(h), base = key_bucket(c, h);
+    const uint32_t fp = az::cache_fp(h), base = az::cache_bucket(c.mask, h);
     uint32_t w[az::kCacheBucket];
 #pragma unroll
     for (int k = 0; k < az::kCacheBucket; ++k)
@@ -418,7 +347,7 @@ __device__ void cache_insert_wave(const CTree& t, const ChessCache& c, int s, in
   int idx = -1;
   if (lane == 0) {
     const uint32_t gen = (uint32_t)__hip_atomic_load(c.ctl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const uint32_t fp = az::cache_fp(h), base = key_bucket(c, h);
+    const uint32_t fp = az::cache_fp(h), base = az::cache_bucket(c.mask, h);
     uint32_t w[az::kCacheBucket];
 #pragma unroll
     for (int k = 0; k < az::kCacheBucket; ++k)
@@ -543,7 +472,7 @@ __device__ void expand_body(const CCfg& g, const CTree& t, const ChessCache& c, 
   if (lane == 0) {
     // normalize_probabilities (mcts/utils.py:4-16): the sum in numpy's
     // pairwise order here, the quotients per lane below
-    sm.sum = pairwise(sorted, n);
+    sm.sum = az::pairwise_sum<AZ_CHESS_MAX_MOVES>(sorted, n);
     if (top + n > g.half_cap) {
       flag(t, az::kErrArena);
       sm.first_s = -1;
@@ -738,18 +667,11 @@ __device__ void dup_tail(const CTree& t, const ChessCache& c, int lane) {
 // NaN above every number (a host evaluator can return anything).
 struct NoiseSmem {
   double d[AZ_CHESS_MAX_MOVES];  // the gammas in component order, then the normalised vector
-  uint32_t cur[az::kMtWords];    // the slot's MT19937 state, read once per draw (every word fetch is an LDS read)
-  uint32_t next[az::kMtWords];   // the next state, staged until a round's used words cross into it
+  uint32_t cur[az::kMtN];    // the slot's MT19937 state, read once per draw (every word fetch is an LDS read)
+  uint32_t next[az::kMtN];   // the next state, staged until a round's used words cross into it
   double invacc;
   int row;
 };
-
-// np.argmax order: NaN above every number, then value, then the lower index
-__device__ __forceinline__ bool argmax_before(double v, int i, double bv, int bi) {
-  if (bv != bv) return v != v && i < bi;
-  if (v != v) return true;
-  return v > bv || (v == bv && i < bi);
-}
 
 // RandomState.dirichlet(alpha * ones(k)) on slot s's MT19937 stream by the
 // slot's wave into sm.d[0..k): az_dirichlet_wave.h's rounds of 64 attempts.
@@ -766,12 +688,12 @@ __device__ __forceinline__ bool dirichlet_wave(const CCfg& g, const CTree& t, in
   const int wpa = az::draw_words_per_attempt(shape);
   auto old = [&](int i) { return sm.cur[i]; };
   auto nw = [&](int i) { return sm.next[i]; };
-  for (int i = lane; i < kMtN; i += 64) sm.cur[i] = m[(size_t)i * slots];
-  int pos = (int)m[(size_t)kMtN * slots];  // wave-uniform, 0..624
+  for (int i = lane; i < az::kMtN; i += 64) sm.cur[i] = m[(size_t)i * slots];
+  int pos = (int)m[(size_t)az::kMtN * slots];  // wave-uniform, 0..624
   __syncthreads();
   int have = 0;
   for (int round = 0; have < k; ++round) {  // every condition below is wave-uniform
-    if (round >= az::kDrawMaxRounds || pos > kMtN) {
+    if (round >= az::kDrawMaxRounds || pos > az::kMtN) {
       if (lane == 0) flag(t, az::kErrDraw);
       return false;
     }
@@ -788,7 +710,7 @@ __device__ __forceinline__ bool dirichlet_wave(const CCfg& g, const CTree& t, in
     for (int q = 0; q < 4; ++q) {
       if (q < wpa) {
         const int i = pos + lane * wpa + q;  // < pos + 256 <= 624 + 256
-        w[q] = az::mt_temper(i < kMtN ? sm.cur[i] : sm.next[i - kMtN]);
+        w[q] = az::mt_temper(i < az::kMtN ? sm.cur[i] : sm.next[i - az::kMtN]);
       }
     }
     double x;
@@ -800,7 +722,7 @@ __device__ __forceinline__ bool dirichlet_wave(const CCfg& g, const CTree& t, in
     bool commit;
     pos = az::draw_round_advance(pos, used, wpa, &commit);
     if (commit) {  // (every lane's word reads of this round are done: the ballot above)
-      for (int i = lane; i < kMtN; i += 64) {
+      for (int i = lane; i < az::kMtN; i += 64) {
         const uint32_t v = sm.next[i];
         sm.cur[i] = v;
         m[(size_t)i * slots] = v;
@@ -810,7 +732,7 @@ __device__ __forceinline__ bool dirichlet_wave(const CCfg& g, const CTree& t, in
     __syncthreads();
   }
   if (lane == 0) {
-    m[(size_t)kMtN * slots] = (uint32_t)pos;
+    m[(size_t)az::kMtN * slots] = (uint32_t)pos;
     double acc = 0.0;  // mtrand's loop: acc = acc + g_j, left to right
     for (int j = 0; j < k; ++j) acc = acc + sm.d[j];
     sm.invacc = 1 / acc;
@@ -904,7 +826,7 @@ __device__ __forceinline__ void select_slot(const CCfg& g, const CTree& t, const
         const double qv = e.N ? e.W / (double)e.N : 0.0;
         const double u = g.c_puct * prior * sq / (double)(1 + e.N);
         const double v = qv + u;
-        if (best == 1 << 30 || argmax_before(v, j, best_v, best)) {
+        if (best == 1 << 30 || az::argmax_before(v, j, best_v, best)) {
           best_v = v;
           best = j;
         }
@@ -914,7 +836,7 @@ __device__ __forceinline__ void select_slot(const CCfg& g, const CTree& t, const
         const double ov = __shfl_xor(best_v, off, 64);
         const int oj = __shfl_xor(best, off, 64);
         // a lane without an edge (1 << 30) ranks below every edge
-        if (oj != 1 << 30 && (best == 1 << 30 || argmax_before(ov, oj, best_v, best))) {
+        if (oj != 1 << 30 && (best == 1 << 30 || az::argmax_before(ov, oj, best_v, best))) {
           best_v = ov;
           best = oj;
         }
@@ -1121,7 +1043,7 @@ __global__ __launch_bounds__(64) void play_kernel(CCfg g, CTree t, CSamples smp,
         if (pi[i] > pi[im]) im = i;
       for (int i = 0; i < n; ++i) pi[i] = i == im ? 1.0 : 0.0;
     } else {
-      const double sum = pairwise(pi, n);  // normalize_probabilities on float64 counts
+      const double sum = az::pairwise_sum<AZ_CHESS_MAX_MOVES>(pi, n);  // normalize_probabilities on float64 counts
       for (int i = 0; i < n; ++i) pi[i] = sum == 0.0 ? 1.0 / (double)n : pi[i] / sum;
     }
     if (po.deterministic) {
@@ -1131,7 +1053,7 @@ __global__ __launch_bounds__(64) void play_kernel(CCfg g, CTree t, CSamples smp,
       chosen = im;
     } else {
       // np.random.choice(edges, 1, p): one random_sample, cumsum, normalise, searchsorted right
-      const double u = po.uniforms ? po.uniforms[s] : mt_uniform(t, s);
+      const double u = po.uniforms ? po.uniforms[s] : az::mt_uniform({t.mt + s, (size_t)t.mt_stride});
       double cdf[1];
       double acc = 0.0, last;
       for (int i = 0; i < n; ++i) acc += pi[i];
@@ -1565,7 +1487,7 @@ int az_chess_engine_create(int device, const az_chess_config* cfg, az_chess_engi
       (rc = e->mem.alloc(&t.path_len, S, false)) || (rc = e->mem.alloc(&t.leaf, S, false)) ||
       (rc = e->mem.alloc(&t.leaf_moves, S * AZ_CHESS_MAX_MOVES, false)) || (rc = e->mem.alloc(&t.leaf_n, S, false)) ||
       (rc = e->mem.alloc(&t.slot_exp, S, false)) || (rc = e->mem.alloc(&t.root_value, S, false)) ||
-      (rc = e->mem.alloc(&t.mt, S * (kMtN + 1), false)) ||
+      (rc = e->mem.alloc(&t.mt, S * (az::kMtN + 1), false)) ||
       (rc = e->mem.alloc(&t.eval_slot, S, false)) || (rc = e->mem.alloc(&t.eval_count, 1, false)) || (rc = e->mem.alloc(&t.slot_q, S, false)) ||
       (rc = e->mem.alloc(&t.stats, az::kStatCount, false)))
     return cleanup(rc);

@@ -1,7 +1,8 @@
-// az_device.h -- board rules, numerics and RNG shared by the gfx950 kernels
-// and the engine's host code.  Every function here is a from-scratch
-// restatement of a reference behaviour; each cites the reference line it
-// must agree with bit for bit (parity: tests/test_engine_gpu.py).
+// az_device.h -- board rules and numerics shared by the gfx950 kernels and
+// the engine's host code (the MT19937 stream: az_mt.h).  Every function here
+// is a from-scratch restatement of a reference behaviour; each cites the
+// reference line it must agree with bit for bit (parity:
+// tests/test_engine_gpu.py).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -271,40 +272,48 @@ AZ_HD int play_c64(Board& b, int a) {
 }
 
 // ---------------------------------------------------------------- numerics
-// numpy float32 add.reduce = identity 0 + pairwise_sum (8 accumulators from
-// n >= 8, 128-element blocks).  normalize_probabilities (mcts/utils.py:4-16)
-// sums the masked network output this way.
-AZ_HD float pairwise_sum_f32(const float* a, int n) {
+// numpy add.reduce of a contiguous float32 / float64 array = identity 0 +
+// pairwise_sum: below 8 elements left to right, up to 128 one block of 8
+// accumulators, above that split at n2 = n / 2, n2 -= n2 % 8 and the halves
+// summed the same way.  normalize_probabilities (mcts/utils.py:4-16) sums the
+// masked network output and the visit counts this way.
+template <typename T>
+AZ_HD T pairwise_block(const T* a, int n) {  // n <= 128
   if (n < 8) {
-    float r = 0.0f;
+    T r = (T)0;
     for (int i = 0; i < n; ++i) r += a[i];
     return r;
   }
-  // n <= kMaxActions = 128: one pairwise block
-  float r[8];
+  T r[8];
   for (int j = 0; j < 8; ++j) r[j] = a[j];
   int i = 8;
   for (; i < n - (n % 8); i += 8)
     for (int j = 0; j < 8; ++j) r[j] += a[i + j];
-  float res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+  T res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
   for (; i < n; ++i) res += a[i];
   return res;
 }
-
-AZ_HD double pairwise_sum_f64(const double* a, int n) {
-  if (n < 8) {
-    double r = 0.0;
-    for (int i = 0; i < n; ++i) r += a[i];
-    return r;
+// n <= MAXN.  The recursion is unrolled at compile time: a half of n <= MAXN
+// elements has at most MAXN / 2 + 8, and a level above MAXN is not compiled
+// (MAXN = 128, Connect-N's action bound, is the block alone; 256, chess's
+// move bound, is two levels: 256 -> 136 -> 76).
+template <int MAXN, typename T>
+AZ_HD T pairwise_sum(const T* a, int n) {
+  if constexpr (MAXN > 128) {
+    if (n > 128) {
+      int n2 = n / 2;
+      n2 -= n2 % 8;
+      return pairwise_sum<MAXN / 2 + 8>(a, n2) + pairwise_sum<MAXN / 2 + 8>(a + n2, n - n2);
+    }
   }
-  double r[8];
-  for (int j = 0; j < 8; ++j) r[j] = a[j];
-  int i = 8;
-  for (; i < n - (n % 8); i += 8)
-    for (int j = 0; j < 8; ++j) r[j] += a[i + j];
-  double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-  for (; i < n; ++i) res += a[i];
-  return res;
+  return pairwise_block(a, n);
+}
+
+// np.argmax order: NaN above every number, then value, then the lower index
+AZ_HD bool argmax_before(double v, int i, double bv, int bi) {
+  if (bv != bv) return v != v && i < bi;
+  if (v != v) return true;
+  return v > bv || (v == bv && i < bi);
 }
 
 // ------------------------------------------------------- synthetic evaluator
@@ -337,20 +346,6 @@ AZ_HD void synth_eval(const Board& b, int A, float* probs, float* value) {
     if (a && a % 12 == 0) w = splitmix64(w);
     probs[a] = (float)((double)(((w >> (5 * (a % 12))) & 31) + 1) / 64.0);
   }
-}
-
-// --------------------------------------------------------------- MT19937
-// Legacy np.random.seed / random_sample (init_genrand + 53-bit double from
-// two outputs), one generator per game; state stored word-major [625][slots]
-// so a wave touching the same word of 64 generators reads one line.
-constexpr int kMtN = 624;
-
-AZ_HD uint32_t mt_temper(uint32_t y) {
-  y ^= y >> 11;
-  y ^= (y << 7) & 0x9d2c5680u;
-  y ^= (y << 15) & 0xefc60000u;
-  y ^= y >> 18;
-  return y;
 }
 
 }  // namespace az

@@ -21,6 +21,12 @@
 // Everything here is AZ_HD: the chess select kernel calls it per lane, and
 // tests/native/chess_noise_check.cpp drives the same functions from a host
 // loop over the 64 lanes.
+//
+// This file owns the schedule only: which lane makes which attempt, which
+// words a round used, and the three-phase order of the regeneration.  The
+// attempt itself (gamma_attempt, draw_words_per_attempt) is az_random.h's;
+// the MT19937 constants, the per-word regeneration formula (mt_regen_word),
+// mt_temper and legacy_double_of are az_mt.h's.
 #pragma once
 #include <stdint.h>
 
@@ -28,9 +34,9 @@
 
 namespace az {
 
-constexpr int kMtWords = 624;
-constexpr int kMtShift = 397;
-constexpr int kMtTail = kMtWords - kMtShift;  // 227
+// the state's size under the name tests/native/chess_noise_check.cpp sizes its
+// host streams with (that check is kept as it was); csrc/ itself uses kMtN
+constexpr int kMtWords = kMtN;
 constexpr int kDrawLanes = 64;
 // a draw's round cap: k <= 256 components need 4 rounds of all-accepted
 // attempts; the acceptance rate of a valid shape is above 85 %, so 64 rounds
@@ -38,7 +44,7 @@ constexpr int kDrawLanes = 64;
 constexpr int kDrawMaxRounds = 64;
 
 // ------------------------------------------------- lane-parallel twist
-// genrand's regeneration, new[i] = far ^ twist(old[i], next) with
+// genrand's regeneration, new[i] = mt_regen_word(old[i], next, far) with
 //   next = old[i + 1] (new[0] for i = 623)
 //   far  = old[i + 397] for i < 227, else new[i - 227]
 // in three phases whose words depend only on old words and on new words of
@@ -47,45 +53,14 @@ constexpr int kDrawMaxRounds = 64;
 //   phase 1  i in [227, 454)  new words [0, 227)            (phase 0)
 //   phase 2  i in [454, 624)  new words [227, 397) and, for i = 623, new[0]
 AZ_HD int mt_phase_begin(int phase) { return phase * kMtTail; }
-AZ_HD int mt_phase_end(int phase) { return phase == 2 ? kMtWords : (phase + 1) * kMtTail; }
-AZ_HD uint32_t mt_twist(uint32_t cur, uint32_t next, uint32_t far) {
-  const uint32_t y = (cur & 0x80000000u) | (next & 0x7fffffffu);
-  return far ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
-}
+AZ_HD int mt_phase_end(int phase) { return phase == 2 ? kMtN : (phase + 1) * kMtTail; }
 // word i of the next state; old(i) / nw(i) read the current / the next state
 template <typename Old, typename New>
 AZ_HD uint32_t mt_twist_word(int i, Old&& old, New&& nw) {
   const uint32_t cur = old(i);
-  const uint32_t next = i == kMtWords - 1 ? nw(0) : old(i + 1);
+  const uint32_t next = i == kMtN - 1 ? nw(0) : old(i + 1);
   const uint32_t far = i < kMtTail ? old(i + kMtShift) : nw(i - kMtTail);
-  return mt_twist(cur, next, far);
-}
-
-// ------------------------------------------------------------ attempts
-AZ_HD int draw_words_per_attempt(double shape) { return shape == 1.0 ? 2 : 4; }
-AZ_HD double legacy_double_of(uint32_t w0, uint32_t w1) {
-  const uint32_t a = w0 >> 5;
-  const uint32_t b = w1 >> 6;
-  return ((double)a * 67108864.0 + (double)b) / 9007199254740992.0;
-}
-// one turn of legacy_standard_gamma's loop on its own (tempered) words w[0..3]
-// (w[0..1] for shape == 1): true = accepted, *x the variate.  inv = 1 / shape.
-AZ_HD bool gamma_attempt(const uint32_t* w, double shape, double inv, double* x) {
-  if (shape == 1.0) {
-    *x = -glibc_log(1.0 - legacy_double_of(w[0], w[1]));
-    return true;
-  }
-  const double U = legacy_double_of(w[0], w[1]);
-  const double V = -glibc_log(1.0 - legacy_double_of(w[2], w[3]));
-  if (U <= 1.0 - shape) {
-    const double X = glibc_pow(U, inv);
-    *x = X;
-    return X <= V;
-  }
-  const double Y = -glibc_log((1.0 - U) / shape);
-  const double X = glibc_pow(1.0 - shape + shape * Y, inv);
-  *x = X;
-  return X <= V + Y;
+  return mt_regen_word(cur, next, far);
 }
 
 // ------------------------------------------------------ round accounting
@@ -107,10 +82,10 @@ AZ_HD int draw_round_used(uint64_t accepted, int have, int k) {
 // one (the used words ran past word 623)
 AZ_HD int draw_round_advance(int pos, int used, int wpa, bool* commit) {
   const int np = pos + used * wpa;
-  *commit = np > kMtWords;
-  return *commit ? np - kMtWords : np;
+  *commit = np > kMtN;
+  return *commit ? np - kMtN : np;
 }
 // a round from pos reads words [pos, pos + 64 wpa): does it need the next state
-AZ_HD bool draw_round_needs_next(int pos, int wpa) { return pos + kDrawLanes * wpa > kMtWords; }
+AZ_HD bool draw_round_needs_next(int pos, int wpa) { return pos + kDrawLanes * wpa > kMtN; }
 
 }  // namespace az

@@ -13,6 +13,7 @@
 
 #include "../../include/az.h"
 #include "az_host.h"
+#include "az_mt.h"
 #include "az_nn.h"
 #include "az_tree.h"
 

@@ -168,8 +168,8 @@ struct CacheDev {
   unsigned long long gen_size = 0;    // inserts per generation; 0 = no eviction
 };
 constexpr int kCacheBucket = 16;  // slots per bucket (cache_log2 >= 4)
-AZ_HD uint32_t cache_bucket(const CacheDev& c, uint64_t h) {
-  return (uint32_t)h & c.mask & ~(uint32_t)(kCacheBucket - 1);
+AZ_HD uint32_t cache_bucket(uint32_t mask, uint64_t h) {  // mask = cap - 1: the bucket's first slot
+  return (uint32_t)h & mask & ~(uint32_t)(kCacheBucket - 1);
 }
 
 // Self-play sample sink, indexed by game id - first_game.

@@ -100,67 +100,6 @@ __device__ __forceinline__ void backup(Edge* E, const int32_t* __restrict__ path
   }
 }
 
-// MT19937, state word-major: word w of slot g at mt[w * slots + g].
-__device__ void mt_seed(const TreeDev& t, int slots, int g, uint32_t seed) {
-  uint32_t prev = seed;
-  t.mt[g] = seed;
-  for (int i = 1; i < kMtN; ++i) {
-    prev = 1812433253u * (prev ^ (prev >> 30)) + (uint32_t)i;
-    t.mt[(size_t)i * slots + g] = prev;
-  }
-  t.mt[(size_t)kMtN * slots + g] = kMtN;  // force a twist on first use
-}
-
-// One twist of a slot's state in place (m: its word 0, words `slots` apart),
-// the serial loop's arithmetic in its order: word i takes words i, i+1 as
-// they were and word i+397 (as it was below i = 227, already new from there
-// on; word 0 is new when i = 623 reads it as i+1).  A batch of kTwistB words
-// loads every operand before its first store -- none of a batch's loads reads
-// a word that batch writes before that word's own update, and the words from
-// earlier batches are stored ahead of them in program order -- so a twist is
-// 39 memory round trips instead of 624 dependent load-store chains (a game's
-// reset twists once: slot_reset).  Batches of 48 words (13 round trips)
-// cost 3% of games/s (profiles/r6/ab_exp5.txt).
-__device__ void mt_twist(uint32_t* m, size_t slots) {
-  constexpr int kTwistB = 16;
-  static_assert(kMtN % kTwistB == 0 && 227 >= kTwistB, "batches never read their own stores");
-  uint32_t cur = m[0];
-  for (int i0 = 0; i0 < kMtN; i0 += kTwistB) {
-    uint32_t nx[kTwistB], far[kTwistB];
-#pragma unroll
-    for (int k = 0; k < kTwistB; ++k) {
-      const int i = i0 + k;
-      nx[k] = m[(size_t)(i + 1 < kMtN ? i + 1 : 0) * slots];
-      far[k] = m[(size_t)(i + 397 < kMtN ? i + 397 : i - 227) * slots];
-    }
-#pragma unroll
-    for (int k = 0; k < kTwistB; ++k) {
-      const uint32_t y = (cur & 0x80000000u) | (nx[k] & 0x7fffffffu);
-      m[(size_t)(i0 + k) * slots] = far[k] ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
-      cur = nx[k];
-    }
-  }
-}
-
-__device__ uint32_t mt_next(const TreeDev& t, int slots, int g) {
-  uint32_t* m = t.mt;
-  uint32_t pos = m[(size_t)kMtN * slots + g];
-  if (pos >= (uint32_t)kMtN) {
-    mt_twist(m + g, (size_t)slots);
-    pos = 0;
-  }
-  const uint32_t y = m[(size_t)pos * slots + g];
-  m[(size_t)kMtN * slots + g] = pos + 1;
-  return mt_temper(y);
-}
-
-// legacy random_sample: ((a >> 5) * 2^26 + (b >> 6)) / 2^53
-__device__ double mt_uniform(const TreeDev& t, int slots, int g) {
-  const uint32_t a = mt_next(t, slots, g) >> 5;
-  const uint32_t b = mt_next(t, slots, g) >> 6;
-  return ((double)a * 67108864.0 + (double)b) / 9007199254740992.0;
-}
-
 __device__ void slot_reset(const GameCfg& g, const TreeDev& t, int s, int64_t gid,
                            uint32_t seed) {
   Board b;
@@ -180,26 +119,12 @@ __device__ void slot_reset(const GameCfg& g, const TreeDev& t, int s, int64_t gi
   t.game_id[s] = gid;
   t.last_move[s] = -1;
   t.last_status[s] = kOngoing;
-  mt_seed(t, t.mt_stride, s, seed);
+  const MtStream rng{t.mt + s, (size_t)t.mt_stride};
+  mt_seed(rng, seed);
   // the reference's play_game draws np.random.rand(1, H, W, 4) building its
   // model between the seed and the game (az_config.rng_skip): the words are
-  // skipped, not drawn -- a twist whenever the index runs out, then the index
-  // (the state mt_next would leave, without 2 dependent round trips per word)
-  if (g.rng_skip > 0) {
-    uint32_t* m = t.mt + s;
-    const size_t slots = (size_t)t.mt_stride;
-    uint32_t pos = kMtN;  // mt_seed's
-    for (int n = g.rng_skip; n > 0;) {
-      if (pos >= (uint32_t)kMtN) {
-        mt_twist(m, slots);
-        pos = 0;
-      }
-      const int k = min(n, kMtN - (int)pos);
-      pos += (uint32_t)k;
-      n -= k;
-    }
-    m[(size_t)kMtN * slots] = pos;
-  }
+  // skipped, not drawn
+  mt_skip(rng, g.rng_skip);
 }
 
 // ------------------------------------------------------------------- select
@@ -251,7 +176,7 @@ __device__ void leaf_tail(const GameCfg& g, const TreeDev& t, const CacheDev& c,
   if (c.enabled) {
     gen = (uint32_t)__hip_atomic_load(c.ctl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     fp = cache_fp(h);
-    base = cache_bucket(c, h);
+    base = cache_bucket(c.mask, h);
 #pragma unroll
     for (int k = 0; k < kCacheBucket; ++k)
       w[k] = __hip_atomic_load(c.state + base + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -350,20 +275,13 @@ __device__ void leaf_tail(const GameCfg& g, const TreeDev& t, const CacheDev& c,
 // dtype (float32, or float64 after the uniform branch: kPrior64), the rest
 // float64 -- and the UCB with that prior; np.argmax treats NaN as the maximum.
 struct SlotMt {  // the slot's MT19937 words, one at a time
-  const TreeDev* t;
-  int s;
-  __device__ uint32_t operator()() { return mt_next(*t, t->mt_stride, s); }
+  MtStream r;
+  __device__ uint32_t operator()() { return mt_next(r); }
 };
 __device__ __forceinline__ double noisy_prior(const GameCfg& g, const Edge& e, double d) {
   const double kept = (e.action & kPrior64) ? (1.0 - g.noise_ratio) * e.prior
                                             : (double)((float)(1.0 - g.noise_ratio) * (float)e.prior);
   return kept + g.noise_ratio * d;
-}
-// np.argmax order: NaN above every number, then value, then the lower index
-__device__ __forceinline__ bool argmax_before(double v, int i, double bv, int bi) {
-  if (bv != bv) return v != v && i < bi;
-  if (v != v) return true;
-  return v > bv || (v == bv && i < bi);
 }
 
 // Serial descent, one lane per game (used when the action space exceeds 64).
@@ -399,7 +317,7 @@ __device__ __forceinline__ void select_body(const GameCfg& g, const TreeDev& t, 
         }
         hn = t.noise_in + ((size_t)s * t.noise_rows + row) * g.A;
       } else {
-        SlotMt r{&t, s};
+        SlotMt r{{t.mt + s, (size_t)t.mt_stride}};
         for (int i = 0; i < cnt; ++i) {
           gam[i] = legacy_standard_gamma(r, g.noise_alpha);
           acc = acc + gam[i];
@@ -580,7 +498,7 @@ __device__ __forceinline__ void select_group_body(const GameCfg& g, const TreeDe
         for (int k = 0; k < cnt; ++k) {  // group-uniform
           double gv = 0.0;
           if (j == 0) {
-            SlotMt r{&t, s};
+            SlotMt r{{t.mt + s, (size_t)t.mt_stride}};
             gv = legacy_standard_gamma(r, g.noise_alpha);
           }
           gv = __shfl(gv, 0, L);
@@ -680,7 +598,7 @@ __device__ void cache_insert_row(const GameCfg& g, const TreeDev& t, const Cache
     const uint64_t h = board_hash(b);
     const uint32_t gen = (uint32_t)__hip_atomic_load(c.ctl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const uint32_t fp = cache_fp(h);
-    const uint32_t base = cache_bucket(c, h);
+    const uint32_t base = cache_bucket(c.mask, h);
     uint32_t w[kCacheBucket];
 #pragma unroll
     for (int k = 0; k < kCacheBucket; ++k)
@@ -824,7 +742,7 @@ __global__ __launch_bounds__(kGameBlock) void expand_kernel(GameCfg g, TreeDev t
     for (int a = 0; a < g.A; ++a)
       if (action_cell(g, b, a) >= 0) masked[nl++] = p[a];
     nm = moves_order(g, b, moves);
-    sum = pairwise_sum_f32(masked, nl);
+    sum = pairwise_sum<kMaxActions>(masked, nl);
   }
   int first = top0;
   if (g.halves > 1) {
@@ -943,7 +861,7 @@ __global__ __launch_bounds__(kGameBlock) void play_kernel(GameCfg g, TreeDev t, 
   } else {
     double c[MAXA];
     for (int i = 0; i < cnt; ++i) c[i] = (double)E[first + i].N;
-    const double sum = pairwise_sum_f64(c, cnt);
+    const double sum = pairwise_sum<kMaxActions>(c, cnt);
     for (int i = 0; i < cnt; ++i) pr[i] = sum == 0.0 ? 1.0 / (double)cnt : c[i] / sum;
   }
   int k;
@@ -952,7 +870,7 @@ __global__ __launch_bounds__(kGameBlock) void play_kernel(GameCfg g, TreeDev t, 
     for (int i = 1; i < cnt; ++i)
       if (pr[i] > pr[k]) k = i;
   } else {
-    const double u = uniforms ? uniforms[s] : mt_uniform(t, t.mt_stride, s);
+    const double u = uniforms ? uniforms[s] : mt_uniform({t.mt + s, (size_t)t.mt_stride});
     double cdf[MAXA];
     double acc = 0.0;
     for (int i = 0; i < cnt; ++i) {

@@ -1,7 +1,7 @@
 """normalize_probabilities with the reference's semantics (mcts/utils.py:4-16).
 
 Host helper for API users; the device restates the same arithmetic
-(csrc/az_device.h pairwise_sum_*).  numpy's float32 sum is pairwise; the
+(csrc/az_device.h pairwise_sum).  numpy's float32 sum is pairwise; the
 zero-sum branch returns a float64 uniform array.
 """
 import numpy as np

@@ -44,6 +44,10 @@ def _compare(r, g, ref, tag):
     # at the start: every slot's leaves coincide), and a table small enough
     # to fill and evict (LRU) while other lanes read it
     (24, 40, 3, 5, 8, 1, 16), (24, 40, 6, 8, 8, 3, 16), (8, 400, 4, 6, 8, 2, 16), (32, 60, 8, 8, 8, 2, 6),
+    # sampled play to the end (every ply's uniform picks the move, two MT19937
+    # words a ply): the game from seed 1002 reaches the cap, so its stream
+    # regenerates a second time at ply 313
+    (8, 340, 3, 3, 1000, 1, 0),
 ])
 def test_chess_selfplay_synthetic_matches_oracle(sims, plies, slots, games, greedy, lanes, cache):
     from custom_alphazero import engine as az
@@ -59,6 +63,8 @@ def test_chess_selfplay_synthetic_matches_oracle(sims, plies, slots, games, gree
     for g in range(games):
         ref = C.play_game(sims, 1000 + g, plies, greedy_ply=greedy)
         _compare(r, g, ref, "synthetic")
+    if greedy > plies:  # the long sampled row: a compared game drew past its stream's first 624 words
+        assert max(int(r["lengths"][g]) for g in range(games)) >= 313
     eng.close()
 
 
