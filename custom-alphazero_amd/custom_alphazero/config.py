@@ -65,6 +65,18 @@ class ConfigMCTS:
     use_solver = False
 
 
+class ConfigSolver:
+    """The exact Connect-N solver on the device (engine.Solver, exact_solvers/):
+    an addition; the reference has ConfigPath.connect4_solver_bin and an opening
+    book instead.  node_budget = 0 leaves the solver off: use_solver and
+    evaluate_with_solver then raise NotImplementedError as before."""
+    node_budget = 0        # search nodes a position may take before it counts as unsolved; 0 = solver off
+    tt_log2 = 24           # transposition table entries (2^k words of 8 bytes)
+    split_stones = 0       # positions with fewer stones are split on the host (0 = the library's default)
+    max_jobs = 0           # largest frontier of a split position (0 = the library's default)
+    device = 0
+
+
 class ConfigModel:
     training_epochs = 1
     batch_size = 256
@@ -91,7 +103,7 @@ class ConfigServing:
     evaluation_games_number = 150   # config.py:89
     replace_min_score = 0.55        # config.py:90
     evaluate_with_mcts = False      # config.py:92
-    evaluate_with_solver = False    # config.py:93 (the solver binary is not part of this package)
+    evaluate_with_solver = False    # config.py:93 (needs ConfigSolver.node_budget > 0)
     # the training loop (train.py, model/tensorflow/train.py)
     minimum_training_size = 2500    # config.py:83
     samples_queue_size = 10000      # config.py:84: the replay window

@@ -114,6 +114,8 @@ EXPORTED = (
     "az_chess_tree_export", "az_chess_trainer_create",
     "az_chess_replay_create", "az_chess_replay_destroy", "az_chess_replay_push", "az_chess_replay_size",
     "az_chess_replay_clear", "az_chess_replay_gather", "az_trainer_step_replay",
+    # the exact Connect-N solver (include/az.h)
+    "az_solver_create", "az_solver_destroy", "az_solver_clear", "az_solver_configure", "az_solver_solve",
 )
 
 _lib = None
@@ -209,6 +211,11 @@ def load_library():
         "az_chess_replay_gather": (ctypes.c_int, [P, P, ctypes.c_int, P, P, P]),
         "az_trainer_step_replay": (ctypes.c_int, [P, P, P, ctypes.c_int, ctypes.c_double, ctypes.c_double,
                                                   ctypes.c_double, ctypes.c_double, P]),
+        "az_solver_create": (ctypes.c_int, [ctypes.c_int] * 5 + [ctypes.POINTER(P)]),
+        "az_solver_destroy": (ctypes.c_int, [P]),
+        "az_solver_clear": (ctypes.c_int, [P]),
+        "az_solver_configure": (ctypes.c_int, [P, ctypes.c_int, I64, ctypes.c_int]),
+        "az_solver_solve": (ctypes.c_int, [P, P, I64, I64, P, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -740,6 +747,64 @@ class ChessReplay:
 
     def clear(self):
         _check(self._L.az_chess_replay_clear(self._h))
+
+
+SOLVER_SOLVED, SOLVER_UNSOLVED = 0, 1
+
+
+class Solver:
+    """The exact Connect-N solver on the device (az_solver_*, csrc/az_solver.hip):
+    alpha-beta over bitboards, one search per GPU lane, a batch of positions
+    per call.  Gravity boards with W <= 16 and W * (H + 1) <= 56.  The
+    transposition table (2^tt_log2 words of 8 bytes) lives as long as the
+    handle; clear() empties it."""
+
+    def __init__(self, height=6, width=7, n=4, tt_log2=24, device=0):
+        L = load_library()
+        handle = ctypes.c_void_p()
+        _check(L.az_solver_create(int(device), int(height), int(width), int(n), int(tt_log2), ctypes.byref(handle)))
+        self._h, self._L = handle, L
+        self.height, self.width, self.n = int(height), int(width), int(n)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.az_solver_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # pragma: no cover - interpreter teardown
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def configure(self, split_stones=0, max_jobs=0, steps_per_launch=0):
+        """split_stones: positions with fewer stones are expanded on the host to
+        those with that many and backed up (a frontier over max_jobs comes back
+        unsolved); steps_per_launch: search steps per kernel launch.  0 keeps a value."""
+        _check(self._L.az_solver_configure(self._h, int(split_stones), int(max_jobs), int(steps_per_launch)))
+
+    def clear(self):
+        _check(self._L.az_solver_clear(self._h))
+
+    def solve(self, boards, node_budget):
+        """boards [count, H, W] int8 as Board.array, +1 the side to move's stones
+        (negate the array when black is to move) -> (scores int32, status uint8,
+        nodes int64), each [count].  status SOLVER_UNSOLVED: the position's search
+        passed node_budget nodes (or its split passed max_jobs); its score is not valid."""
+        b = np.ascontiguousarray(boards, np.int8).reshape(-1, self.height, self.width)
+        count = len(b)
+        scores = np.zeros(count, np.int32)
+        status = np.zeros(count, np.uint8)
+        nodes = np.zeros(count, np.int64)
+        _check(self._L.az_solver_solve(self._h, _ptr(b), count, int(node_budget), _ptr(scores), _ptr(status),
+                                       _ptr(nodes)))
+        return scores, status, nodes
 
 
 class ChessEngine:

@@ -12,8 +12,15 @@
   only difference; the draw count per move is the reference's).  Dirichlet
   root noise (ConfigMCTS.enable_dirichlet_noise) is drawn the same way: the
   search's root-noise vectors, then play's draw, from the game's stream.
-The exact-solver scoring path needs the refused c4solver binary (SURVEY.md
-section 8c) and raises NotImplementedError.
+The exact-solver scoring path (evaluate.py:53-59: how the solver ranks the
+current model's raw-policy moves) runs on the device solver
+(exact_solvers/c4_exact_solver.py) once ConfigSolver.node_budget > 0; with
+the default 0 it raises NotImplementedError, as it does for chess, for boards
+the solver does not take and together with evaluate_with_mcts
+(evaluate.py:100-102).  The one deviation from the reference: it has an
+opening book, this has a budget -- a move whose position comes back unsolved
+is left out of the mean and counted; `solver_report` holds {"scored",
+"unsolved"} of the last call, and with nothing scored the solver score is None.
 
 The game is ConfigGeneral.game, read at call time (evaluate.py:16-26 picks
 Board, Move and get_all_possible_moves by it): "connect_n" as above, "chess"
@@ -39,6 +46,7 @@ batched kernels.encode.  deterministic=True gives the sequential loop's
 per-game results and final positions; stochastic play draws from each game's
 own stream, one draw per move as Connect-N.
 """
+from copy import deepcopy
 from typing import List, Optional, Tuple
 
 import numpy as np
@@ -48,10 +56,29 @@ from custom_alphazero.config import (ConfigConnectN, ConfigGeneral, ConfigMCTS, 
                                      ConfigServing, check_mcts_config)
 from custom_alphazero.connect_n.board import Board
 from custom_alphazero.connect_n.move import Move
+from custom_alphazero.exact_solvers import c4_exact_solver as exact
 from custom_alphazero.mcts.mcts import MCTS, root_noise_rows
 from custom_alphazero.mcts.utils import normalize_probabilities
 
 get_all_possible_moves = Board.get_all_possible_moves
+
+# moves the solver scored / could not score within its budget, in the last arena call
+solver_report = {"scored": 0, "unsolved": 0}
+
+
+def _check_solver(evaluate_with_mcts: bool = False):
+    """The refusals of solver scoring, all NotImplementedError."""
+    if _game()[2]:
+        raise NotImplementedError("solver scoring is not implemented for chess")
+    exact.check_solver_config()
+    if evaluate_with_mcts:
+        raise NotImplementedError("solver scoring under MCTS is not implemented (evaluate.py:100-102)")
+
+
+def _solver_move_score(ranked_moves_indexes, board: Board, move: Move) -> float:
+    """evaluate.py:55-59, the reference's own expression: the argsort result
+    indexed by the move's index."""
+    return 1 - (ranked_moves_indexes[board.moves.index(move)] + 1) / len(board.moves)
 
 
 def _game():
@@ -137,11 +164,17 @@ def _policy_move(model, board: Board, all_possible_moves: List[Move], determinis
 def _single_game_evaluation(current_model, previous_model, game_index: int,
                             all_possible_moves: List[Move], evaluate_with_mcts: bool,
                             evaluate_with_solver: bool, deterministic: bool,
-                            rng=None, trace: Optional[list] = None) -> Tuple[int, Optional[List[float]]]:
+                            rng=None, trace: Optional[list] = None,
+                            report: Optional[dict] = None) -> Tuple[int, Optional[List[float]]]:
     """evaluate.py:29-98.  Additions: `rng` replaces the global np.random;
-    `trace` collects the final board's array."""
+    `trace` collects the final board's array; `report` counts the scored and
+    unsolved moves (default: solver_report, reset)."""
+    solver_scores = []
     if evaluate_with_solver:
-        raise NotImplementedError("solver scoring needs the c4solver binary (not run here)")
+        _check_solver()
+        if report is None:
+            report = solver_report
+            report.update(scored=0, unsolved=0)
     rng = np.random if rng is None else rng
     if _game()[2]:
         return _single_chess_game(current_model, previous_model, game_index, all_possible_moves,
@@ -151,6 +184,13 @@ def _single_game_evaluation(current_model, previous_model, game_index: int,
         board = Board()
         while not board.is_game_over():
             move = _policy_move(model, board, all_possible_moves, deterministic, rng)
+            if evaluate_with_solver and model is current_model:
+                try:
+                    ranked_moves_indexes, _ = exact.exact_ranked_moves_and_value(board)
+                    solver_scores.append(_solver_move_score(ranked_moves_indexes, board, move))
+                    report["scored"] += 1
+                except exact.SolverBudgetError:
+                    report["unsolved"] += 1
             board.play(move, keep_same_player=True)
             if not board.is_game_over():
                 model = previous_model if model is current_model else current_model
@@ -182,8 +222,8 @@ def _single_game_evaluation(current_model, previous_model, game_index: int,
         trace.append(board.array.copy())
     result = board.get_result(keep_same_player=True)
     if result:
-        return (1 if current_model is model else -1), []
-    return 0, []
+        return (1 if current_model is model else -1), solver_scores
+    return 0, solver_scores
 
 
 def _score(results) -> float:
@@ -198,12 +238,17 @@ def evaluate_two_models(model, other_model, evaluate_with_mcts: bool = False,
                         evaluate_with_solver: bool = False, deterministic: bool = False):
     """evaluate.py:101-134: (score of `model`, solver score or None)."""
     if evaluate_with_solver:
-        raise NotImplementedError("solver scoring needs the c4solver binary (not run here)")
+        _check_solver(evaluate_with_mcts)
+        solver_report.update(scored=0, unsolved=0)
     all_possible_moves = _game()[1]()
-    results = [_single_game_evaluation(model, other_model, g, all_possible_moves,
-                                       evaluate_with_mcts, False, deterministic)[0]
-               for g in range(ConfigServing.evaluation_games_number)]
-    return _score(results), None
+    results, solver_scores = [], []
+    for g in range(ConfigServing.evaluation_games_number):
+        result, scores = _single_game_evaluation(model, other_model, g, all_possible_moves, evaluate_with_mcts,
+                                                 evaluate_with_solver, deterministic, report=solver_report)
+        results.append(result)
+        solver_scores.extend(scores)
+    solver_score = np.mean(solver_scores) if evaluate_with_solver and len(solver_scores) else None
+    return _score(results), solver_score
 
 
 def _arena_engine(model, n_slots: int) -> az.Engine:
@@ -312,10 +357,18 @@ def _chess_arena_batched(model, other_model, n: int, evaluate_with_mcts: bool, d
 
 def evaluate_two_models_batched(model, other_model, n_games: Optional[int] = None,
                                 evaluate_with_mcts: bool = False, deterministic: bool = True,
-                                seed: int = 0, trace: Optional[list] = None):
+                                seed: int = 0, trace: Optional[list] = None,
+                                evaluate_with_solver: bool = False, solver_scores: Optional[list] = None):
     """All games at once.  Returns (score of `model`, per-game results);
-    `trace` collects the final boards' arrays (chess: az_chess_pos records) in game order."""
+    `trace` collects the final boards' arrays (chess: az_chess_pos records) in game order.
+    evaluate_with_solver: `solver_scores` collects the sequential loop's solver
+    score of every scored move of `model`, in game order then ply order; the
+    positions are gathered while the games run and solved in one solver call."""
     n = int(n_games or ConfigServing.evaluation_games_number)
+    if evaluate_with_solver:
+        _check_solver(evaluate_with_mcts)
+        solver_report.update(scored=0, unsolved=0)
+    scored_moves = [[] for _ in range(n)]  # per game: (board before the move, the move) of `model`
     if _game()[2]:
         return _chess_arena_batched(model, other_model, n, evaluate_with_mcts, deterministic, seed, trace)
     all_moves = get_all_possible_moves()
@@ -345,6 +398,8 @@ def evaluate_two_models_batched(model, other_model, n_games: Optional[int] = Non
                         move = boards[g].moves[int(np.argmax(legal))]
                     else:
                         move = rngs[g].choice(boards[g].moves, 1, p=legal).item()
+                    if evaluate_with_solver and s == 0:
+                        scored_moves[g].append((deepcopy(boards[g]), move))
                     boards[g].play(move, keep_same_player=True)
             else:
                 eng = engines[s]
@@ -382,4 +437,14 @@ def evaluate_two_models_batched(model, other_model, n_games: Optional[int] = Non
         r = boards[g].get_result(keep_same_player=True)
         results.append(0 if not r else (1 if last_side[g] == 0 else -1))
     _ = A
+    if evaluate_with_solver:
+        pairs = [p for game in scored_moves for p in game]
+        ranked = exact.exact_ranked_moves_and_value_batch([b for b, _ in pairs])
+        for (board, move), r in zip(pairs, ranked):
+            if r is None:
+                solver_report["unsolved"] += 1
+                continue
+            solver_report["scored"] += 1
+            if solver_scores is not None:
+                solver_scores.append(_solver_move_score(r[0], board, move))
     return _score(results), results

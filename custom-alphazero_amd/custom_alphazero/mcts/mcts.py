@@ -33,6 +33,28 @@ class SyntheticEvaluator:
     (compiled into libaz) instead of a network -- used for parity runs."""
 
 
+class SolverEvaluator:
+    """MCTS(use_solver=True)'s evaluator (mcts.py:126-129): a callable
+    model(x) -> (probabilities, values) that answers every leaf of a simulation
+    with exact_policy_and_value, the whole batch from one solver call.  Each
+    board is recovered from its full_state planes (Board.from_one_hot, and the
+    turn plane).  A position over ConfigSolver.node_budget raises
+    SolverBudgetError, which the search re-raises as the host evaluator's error."""
+
+    def __init__(self, all_possible_moves):
+        self.all_possible_moves = all_possible_moves
+
+    def __call__(self, x):
+        from custom_alphazero.exact_solvers import c4_exact_solver as exact
+        boards = []
+        for planes in np.asarray(x):
+            board = Board(Board.from_one_hot(planes[..., :-1]).astype(np.int8))
+            board.turn = board.white if planes[0, 0, -1] > 0 else board.black
+            boards.append(board)
+        policies, values = exact.exact_policy_and_value_batch(boards, self.all_possible_moves)
+        return policies.astype(np.float32), values.astype(np.float32)
+
+
 class UCTEdge:
     """Read-only view of one device edge (reference mcts.py:22-55)."""
 
@@ -135,7 +157,11 @@ class MCTS:
     def __init__(self, board: Board, all_possible_moves: List[Move], concurrency: bool = False,
                  plays_inferences: Optional[dict] = None, model=None, use_solver: bool = False):
         if use_solver:
-            raise NotImplementedError("the exact solver (c4solver) is not on the device path")
+            # the solver in place of the model (mcts.py:126-129); NotImplementedError while
+            # ConfigSolver.node_budget is 0 or for a board the solver does not take
+            from custom_alphazero.exact_solvers.c4_exact_solver import check_solver_config
+            check_solver_config()
+            model = SolverEvaluator(all_possible_moves)
         self.board = deepcopy(board)
         self.all_possible_moves = all_possible_moves
         self.concurrency = concurrency

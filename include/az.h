@@ -310,6 +310,33 @@ int az_trainer_read(az_trainer* tr, int what, const char* name, float* out, int6
 int az_trainer_step(az_trainer* tr, const float* x, const float* pi, const float* z, int n,
                     double lr, double momentum, double l2, double bn_momentum, float* losses);
 
+/* The exact Connect-N solver (exact_solvers/c4_exact_solver.py, which shells out to the c4solver
+ * binary): alpha-beta over bitboards, one serial search per GPU lane, many positions at once
+ * (csrc/az_solver.h, az_solver.hip; DESIGN.md "Exact solver").  Gravity boards with H, W >= 2,
+ * W <= 16, W * (H + 1) <= 56 and 2 <= n <= max(H, W); anything else is AZ_E_INVALID.  A score is for
+ * the side to move: the winner of a game whose last stone leaves t stones on the board scores
+ * (H*W + 2 - t) / 2, the loser the negative, a draw 0 (the c4solver's numbers on 7x6).  The
+ * transposition table (2^tt_log2 words of 8 bytes, tt_log2 4..30) lives as long as the handle.  A
+ * solver runs on a stream of its own; every call is synchronous. */
+typedef struct az_solver az_solver;
+#define AZ_SOLVER_SOLVED 0
+#define AZ_SOLVER_UNSOLVED 1   /* node budget or max_jobs exceeded: score is not valid */
+int az_solver_create(int device, int height, int width, int n, int tt_log2, az_solver** out);
+int az_solver_destroy(az_solver* s);
+/* empties the table */
+int az_solver_clear(az_solver* s);
+/* split_stones: a position with fewer stones is expanded on the host to the positions with that many,
+ * each solved as a job of its own, and backed up (more than max_jobs of them: unsolved, not searched);
+ * steps_per_launch: search steps a lane runs per kernel launch.  0 keeps the default */
+int az_solver_configure(az_solver* s, int split_stones, int64_t max_jobs, int steps_per_launch);
+/* boards [count][H][W] int8, row 0 the top row as Board.array, +1 the side to move's stones, -1 the
+ * other side's (the caller negates the array when black is to move); a position that is already won,
+ * full, floating or has a stone count of the wrong parity is AZ_E_INVALID naming its index.
+ * node_budget per job (> 0).  Out: scores [count] int32, status [count] uint8, nodes [count] int64
+ * (the position's jobs summed; informative: it depends on what the table held and on scheduling). */
+int az_solver_solve(az_solver* s, const int8_t* boards, int64_t count, int64_t node_budget,
+                    int32_t* scores, uint8_t* status, int64_t* nodes);
+
 #ifdef __cplusplus
 }
 #endif
