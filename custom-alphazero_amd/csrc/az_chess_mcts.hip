@@ -125,15 +125,7 @@ struct ChessKey {
 };
 static_assert(sizeof(ChessKey) == 96, "ChessKey is 6 uint4");
 constexpr int kPayFloats = AZ_CHESS_MAX_MOVES + 4;  // priors in action order [n], then value at [256]
-struct ChessCache {
-  ChessKey* keys = nullptr;      // [cap]
-  uint32_t* state = nullptr;     // [cap] az_tree.h cache_word (fingerprint, generation, status)
-  float* pay = nullptr;          // [cap][kPayFloats]
-  uint32_t mask = 0;
-  int enabled = 0;
-  unsigned long long* ctl = nullptr;  // [0] generation, [1] inserts since the clear, [2] into empty slots
-  unsigned long long gen_size = 0;
-};
+using ChessCache = az::Cache<ChessKey>;  // az_cache.h; a payload is [kPayFloats]
 
 struct CSamples {
   int64_t first_game = 0, n_games = 0;
@@ -250,7 +242,7 @@ __global__ void tree_release_kernel(CTree t, int n, const int32_t* slots) {
 }
 
 // ------------------------------------------------- transposition cache
-// (az_tree.h's scheme: 16-slot buckets, LRU eviction by generations, a hit
+// (az_cache.h's scheme: 16-slot buckets, LRU eviction by generations, a hit
 // refreshes its entry into the current generation.)  The select wave that
 // hits copies the payload into its slot's leaf_pay right away, so a reader
 // holds an entry only for the few microseconds between its probe (which
@@ -282,47 +274,7 @@ __device__ bool cache_probe_wave(const CTree& t, const ChessCache& c, int s, int
                                  int initial, uint64_t h, int n) {
   int idx = -1;
   if (lane == 0) {
-    const uint32_t gen = (uint32_t)__hip_atomic_load(c.ctl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const uint32_t fp = az::cache_fp(h), base = az::cache_bucket(c.mask, h);
-    uint32_t w[az::kCacheBucket];
-#pragma unroll
-    for (int k = 0; k < az::kCacheBucket; ++k)
-      w[k] = __hip_atomic_load(c.state + base + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    int hit = -1;
-    uint32_t hst = 0;
-    uint32_t cm = 0;  // fingerprint matches (buckets fill in slot order), then one acquire, then the keys
-    bool stop = false;
-#pragma unroll
-    for (int k = 0; k < az::kCacheBucket; ++k) {
-      const uint32_t st = w[k];
-      if (stop) continue;
-      if (st == az::kCacheEmpty) stop = true;
-      else if ((st & 3u) == az::kCacheReady && (st >> 16) == fp) cm |= 1u << k;
-    }
-    if (cm) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      for (; cm; cm &= cm - 1) {
-        const int k = __builtin_ctz(cm);
-        if (same_key(c.keys + base + k, key, initial)) {
-          hit = k;
-#pragma unroll
-          for (int kk = 0; kk < az::kCacheBucket; ++kk)
-            if (kk == k) hst = w[kk];
-          break;
-        }
-      }
-    }
-    if (hit >= 0 && az::cache_age(hst, gen) != 0) {
-      // into the current generation (the LRU stamp); the CAS must win, or find
-      // the entry moved there by another reader and still this key
-      const uint32_t want = az::cache_word(fp, gen, az::kCacheReady);
-      const uint32_t prev = atomicCAS(c.state + base + hit, hst, want);
-      if (prev != hst) {
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        if (!(prev == want && same_key(c.keys + base + hit, key, initial))) hit = -1;
-      }
-    }
-    idx = hit >= 0 ? (int)(base + hit) : -1;
+    idx = az::cache_lookup(c, az::cache_load(c, h), [&](uint32_t i) { return same_key(c.keys + i, key, initial); });
   }
   idx = __shfl(idx, 0);
   if (idx < 0) return false;
@@ -336,7 +288,7 @@ __device__ bool cache_probe_wave(const CTree& t, const ChessCache& c, int s, int
 
 // plays_inferences[repr(board)] = (priors, value) (mcts.py:142) by the wave of
 // the leaf's network row owner: the bucket's first empty slot, else its least
-// recently used entry kCacheEvictAge+ generations old (az_tree.h); dropped
+// recently used entry kCacheEvictAge+ generations old (az_cache.h); dropped
 // when every entry is in use
 __device__ void cache_insert_wave(const CTree& t, const ChessCache& c, int s, int lane, const float* sorted, int n,
                                   float value) {
@@ -346,41 +298,12 @@ __device__ void cache_insert_wave(const CTree& t, const ChessCache& c, int s, in
   const uint64_t h = key_hash(q, initial);
   int idx = -1;
   if (lane == 0) {
-    const uint32_t gen = (uint32_t)__hip_atomic_load(c.ctl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const uint32_t fp = az::cache_fp(h), base = az::cache_bucket(c.mask, h);
-    uint32_t w[az::kCacheBucket];
-#pragma unroll
-    for (int k = 0; k < az::kCacheBucket; ++k)
-      w[k] = __hip_atomic_load(c.state + base + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    uint32_t tried = 0;
-    bool empty = false;
-    for (int attempt = 0; attempt < az::kCacheBucket && idx < 0; ++attempt) {
-      int pick = -1;
-      uint32_t pst = 0, page = 0;
-      bool pempty = false;
-#pragma unroll
-      for (int k = 0; k < az::kCacheBucket; ++k) {
-        const uint32_t st = w[k];
-        if (pempty || ((tried >> k) & 1u)) continue;
-        if (st == az::kCacheEmpty) {
-          pick = k, pst = st, pempty = true;
-        } else if (c.gen_size) {
-          const uint32_t age = az::cache_age(st, gen);
-          if (age >= az::kCacheEvictAge && age > page) pick = k, pst = st, page = age;
-        }
-      }
-      if (pick < 0) break;
-      if (atomicCAS(c.state + base + pick, pst, az::cache_word(fp, gen, az::kCacheClaimed)) == pst) {
-        idx = (int)(base + pick);
-        empty = pempty;
-      } else {
-        tried |= 1u << pick;
-      }
-    }
+    const az::CacheBucket bk = az::cache_load(c, h);
+    const az::CacheClaim cl = az::cache_claim(c, bk);
+    idx = cl.idx;
     if (idx >= 0) {
-      if (empty) atomicAdd(c.ctl + 2, 1ull);
-      const unsigned long long m = atomicAdd(c.ctl + 1, 1ull) + 1;
-      if (c.gen_size && m % c.gen_size == 0) atomicAdd(c.ctl, 1ull);
+      if (cl.was_empty) atomicAdd(c.ctl + 2, 1ull);
+      az::cache_turn(c, atomicAdd(c.ctl + 1, 1ull) + 1);
       atomicAdd(t.stats + az::kStatCacheInserts, 1ull);
     }
   }
@@ -1528,25 +1451,11 @@ int az_chess_engine_create(int device, const az_chess_config* cfg, az_chess_engi
   }
   t.mt_stride = g.slots;
   // the transposition cache (mcts.py:122-143 on chess boards)
-  if (c.cache_log2 < 0 || c.cache_log2 > 28 || (c.cache_log2 > 0 && c.cache_log2 < 4))
-    return cleanup(az::fail_abi(AZ_E_INVALID, "cache_log2 must be 0 (no cache) or 4..28"));
+  // no reader window (0): a reader holds an entry only between its probe and
+  // its payload copy, inside one select launch, so generations are cap/16 inserts
+  if ((rc = az::cache_create(e->mem, e->cache, c.cache_log2, 28, kPayFloats, 0))) return cleanup(rc);
   t.leaf_pay = nullptr;
-  if (c.cache_log2 > 0) {
-    const size_t cap = (size_t)1 << c.cache_log2;
-    ChessCache& cc = e->cache;
-    if ((rc = e->mem.alloc(&cc.keys, cap, false)) || (rc = e->mem.alloc(&cc.state, cap, false)) ||
-        (rc = e->mem.alloc(&cc.pay, cap * kPayFloats, false)) || (rc = e->mem.alloc(&cc.ctl, 4, false)) ||
-        (rc = e->mem.alloc(&t.leaf_pay, S * kPayFloats, false)))
-      return cleanup(rc);
-    cc.mask = (uint32_t)(cap - 1);
-    cc.enabled = 1;
-    // LRU by generations of cap/16 inserts (a reader holds an entry only
-    // between its probe and its payload copy, inside one select launch)
-    cc.gen_size = cap / az::kCacheGenDiv;
-    if (hipMemset(cc.state, 0, cap * sizeof(uint32_t)) != hipSuccess ||
-        hipMemset(cc.ctl, 0, 4 * sizeof(unsigned long long)) != hipSuccess)
-      return cleanup(az::fail_abi(AZ_E_HIP, "cache memset failed"));
-  }
+  if (e->cache.enabled && (rc = e->mem.alloc(&t.leaf_pay, S * kPayFloats, false))) return cleanup(rc);
   e->net.depth = c.depth;
   // depth 0: the fp16x2 chain runs the heads' 1x1 convs inside the last
   // block's conv2, so a tower without blocks takes the fp32 MFMA path
@@ -1616,8 +1525,8 @@ int az_chess_engine_set_evaluator(az_chess_engine* e, az_eval_fn fn, void* user)
   e->host_fn = fn;
   e->host_user = user;
   if (e->cache.state) {  // cached outputs belong to the previous evaluator
-    AZ_HIP(hipMemset(e->cache.state, 0, ((size_t)e->cache.mask + 1) * sizeof(uint32_t)));
-    AZ_HIP(hipMemset(e->cache.ctl, 0, 4 * sizeof(unsigned long long)));
+    AZ_TRY(az::cache_clear(e->cache, nullptr));
+    AZ_HIP(hipStreamSynchronize(nullptr));
   }
   return 0;
 }
@@ -1629,8 +1538,8 @@ int az_chess_engine_set_weights(az_chess_engine* e, const az_tensor* tensors, in
   int rc;
   if ((rc = sync_lanes(e))) return rc;
   if (e->cache.state) {  // a new model empties plays_inferences (self_play.py:145-146)
-    AZ_HIP(hipMemset(e->cache.state, 0, ((size_t)e->cache.mask + 1) * sizeof(uint32_t)));
-    AZ_HIP(hipMemset(e->cache.ctl, 0, 4 * sizeof(unsigned long long)));
+    AZ_TRY(az::cache_clear(e->cache, nullptr));
+    AZ_HIP(hipStreamSynchronize(nullptr));
   }
   return az::load_network(e->net, tensors, n, AZ_CHESS_PLANES, 64, AZ_CHESS_ACTIONS, e->cfg.bn_epsilon,
                           e->mem);
@@ -1705,8 +1614,7 @@ int az_chess_stats(az_chess_engine* e, az_stats* st) {
   int rc;
   if ((rc = sync_lanes(e))) return rc;
   unsigned long long h[az::kStatCount];
-  if ((rc = az::read_common_stats(st, h, e->t.stats, e->t.game_id, e->g.slots, e->cache.ctl, e->cache.gen_size,
-                                  e->cache.mask)))
+  if ((rc = az::read_common_stats(st, h, e->t.stats, e->t.game_id, e->g.slots, e->cache)))
     return rc;
   st->issued_flop_per_board = e->net.use_tower && e->net.tower ? e->net.layout.main.issued_flop_per_board : 0.0;
   st->tower_small_max_boards = -1;  // (chess: one tile height)

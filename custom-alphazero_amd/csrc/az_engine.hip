@@ -37,8 +37,8 @@ const int g_hw_queues_at_load = read_hw_queues();
 
 // A lane = a contiguous group of slots searched on its own HIP stream.  Lanes
 // share the network, the transposition cache, the sample sink and the
-// counters; each owns its eval queue, per-simulation dedup table and slices
-// of the activation buffers.  Two lanes keep the GPU busy across each
+// counters; each owns its eval queues and slices of the activation
+// buffers.  Two lanes keep the GPU busy across each
 // other's launch tails and small latency-bound kernels; results do not
 // depend on the lane count (each game's search only reads its own tree and
 // the evaluator is deterministic per board).
@@ -186,7 +186,7 @@ int simulate(az_engine* e, Lane& L) {
   if (L.tree_timer.enabled) L.tree_timer.end(s, 1);
   const az::Board* rows = L.t.eval_board;
   const int32_t* n_rows = L.t.eval_count;
-  if (e->cache.enabled) {  // the select launch resolved its duplicate boards (dedup_tail)
+  if (e->cache.enabled) {  // the misses' rows (a board two slots miss on in one simulation has two)
     rows = L.t.nn_board;
     n_rows = L.t.nn_count;
   }
@@ -238,8 +238,7 @@ int cache_clear(az_engine* e) {
   if (!e->cache.state) return 0;
   int rc;
   if ((rc = sync_all(e))) return rc;
-  AZ_HIP(hipMemsetAsync(e->cache.state, 0, ((size_t)e->cache.mask + 1) * sizeof(uint32_t), e->stream));
-  AZ_HIP(hipMemsetAsync(e->cache.ctl, 0, 4 * sizeof(unsigned long long), e->stream));
+  if ((rc = az::cache_clear(e->cache, e->stream))) return rc;
   AZ_HIP(hipStreamSynchronize(e->stream));
   return 0;
 }
@@ -340,7 +339,7 @@ int upload_new(az::DeviceAllocs& owned, T** dst, const std::vector<T>& src) {
 }
 
 // Lane views: per-slot arrays offset to the lane's first slot; with more than
-// one lane each gets its own eval-queue counters and dedup table.
+// one lane each gets its own eval-queue counters.
 int make_lane(az_engine* e, Lane* L, int first, int n, bool own_queue) {
   const az::GameCfg& g = e->g;
   L->first = first;
@@ -772,29 +771,14 @@ int az_engine_create(int device, const az_config* cfg, az_engine** out) {
   // leaf records start untagged (leaf_epoch counts from 1)
   if (hipMemset(t.leaf_src, 0, S * sizeof(uint64_t)) != hipSuccess)
     return cleanup(fail(AZ_E_HIP, "memset failed"));
-  if (c.cache_log2 < 0 || c.cache_log2 > 30 || (c.cache_log2 > 0 && c.cache_log2 < 4))
-    return cleanup(fail(AZ_E_INVALID, "cache_log2 must be 0 (no cache) or 4..30"));
-  if (c.cache_log2 > 0) {
-    const size_t cap = (size_t)1 << c.cache_log2;
-    az::CacheDev& cd = e->cache;
-    if ((rc = e->mem.alloc(&cd.keys, cap, false)) || (rc = e->mem.alloc(&cd.state, cap, false)) ||
-        (rc = e->mem.alloc(&cd.pay, cap * (A + 1), false)) || (rc = e->mem.alloc(&cd.ctl, 4, false)))
-      return cleanup(rc);
-    cd.mask = (uint32_t)(cap - 1);
-    cd.enabled = 1;
-    // LRU eviction by generations of cap/kCacheGenDiv inserts -- or, for a
-    // larger batch, of more than three moves of every slot's inserts (the
-    // lane-drift bound, az_tree.h: configs[2]'s 8192 x S=200 and configs[3]'s
-    // 4096 x S=400 need it at 2^26 entries) while at most cap/4 (four
-    // generations per turnover keep the LRU order meaningful); otherwise the
-    // table only fills (entries are never overwritten)
-    const unsigned long long bound = 3ull * (unsigned long long)g.slots * (unsigned long long)g.sims + 1;
-    const unsigned long long gen = std::max<unsigned long long>(cap / az::kCacheGenDiv, bound);
-    cd.gen_size = gen <= cap / 4 ? gen : 0;
-    if (hipMemset(cd.state, 0, cap * sizeof(uint32_t)) != hipSuccess ||
-        hipMemset(cd.ctl, 0, 4 * sizeof(unsigned long long)) != hipSuccess)
-      return cleanup(fail(AZ_E_HIP, "cache memset failed"));
-  }
+  // LRU eviction by generations of cap/kCacheGenDiv inserts -- or, for a
+  // larger batch, of more than three moves of every slot's inserts: select
+  // finds an entry and expand reads its payload one launch later, on lanes
+  // that move events keep within two moves of each other (configs[2]'s 8192 x
+  // S=200 and configs[3]'s 4096 x S=400 need it at 2^26 entries)
+  if ((rc = az::cache_create(e->mem, e->cache, c.cache_log2, 30, A + 1,
+                             3ull * (unsigned long long)g.slots * (unsigned long long)g.sims)))
+    return cleanup(rc);
   if (hipMemset(t.stats, 0, az::kStatCount * sizeof(unsigned long long)) != hipSuccess ||
       hipMemset(t.eval_count, 0, az::kCountWords * sizeof(int32_t)) != hipSuccess ||
 
@@ -979,8 +963,7 @@ int az_stats_get(az_engine* e, az_stats* st) {
   int rc;
   if ((rc = sync_all(e))) return rc;
   unsigned long long h[az::kStatCount];
-  if ((rc = az::read_common_stats(st, h, e->t.stats, e->t.game_id, e->g.slots, e->cache.ctl, e->cache.gen_size,
-                                  e->cache.mask)))
+  if ((rc = az::read_common_stats(st, h, e->t.stats, e->t.game_id, e->g.slots, e->cache)))
     return rc;
   std::vector<az::ConvTimer*> timers = {&e->timer, &e->whole.timer};
   for (Lane* L : e->lanes)

@@ -80,6 +80,37 @@ struct DeviceAllocs {
   }
 };
 
+// The transposition cache of an engine (az_cache.h): 2^cache_log2 entries of
+// pay_floats payload floats each, empty; cache_log2 = 0 leaves c off.  max_log2
+// is the engine's limit, reader_window_inserts its cache_gen_size argument.
+template <typename Key>
+int cache_create(DeviceAllocs& mem, Cache<Key>& c, int cache_log2, int max_log2, size_t pay_floats,
+                 unsigned long long reader_window_inserts) {
+  if (cache_log2 < 0 || cache_log2 > max_log2 || (cache_log2 > 0 && cache_log2 < 4))
+    return fail_abi(AZ_E_INVALID, "cache_log2 must be 0 (no cache) or 4.." + std::to_string(max_log2));
+  if (cache_log2 == 0) return 0;
+  const size_t cap = (size_t)1 << cache_log2;
+  AZ_TRY(mem.alloc(&c.keys, cap, false));
+  AZ_TRY(mem.alloc(&c.state, cap, false));
+  AZ_TRY(mem.alloc(&c.pay, cap * pay_floats, false));
+  AZ_TRY(mem.alloc(&c.ctl, 4, false));
+  c.mask = (uint32_t)(cap - 1);
+  c.enabled = 1;
+  c.gen_size = cache_gen_size(cap, reader_window_inserts);
+  if (hipMemset(c.state, 0, cap * sizeof(uint32_t)) != hipSuccess ||
+      hipMemset(c.ctl, 0, 4 * sizeof(unsigned long long)) != hipSuccess)
+    return fail_abi(AZ_E_HIP, "cache memset failed");
+  return 0;
+}
+
+// Empties the cache (every state word Empty, the control words 0) on stream s;
+// the caller keeps the cache's kernels away before and waits for s after.
+inline int cache_clear(const CacheCore& c, hipStream_t s) {
+  AZ_HIP(hipMemsetAsync(c.state, 0, ((size_t)c.mask + 1) * sizeof(uint32_t), s));
+  AZ_HIP(hipMemsetAsync(c.ctl, 0, 4 * sizeof(unsigned long long), s));
+  return 0;
+}
+
 // Each engine's own advice, appended to the flag's name in the message.
 struct ErrorHints {
   const char* arena;   // after " arena-overflow"
@@ -115,7 +146,7 @@ inline int device_error_status(unsigned long long* stats, const ErrorHints& hint
 // reads the newest complete snapshot (az_move_clock.h), so it never waits for
 // the move that is running.  A lane plays move m only once every other lane
 // has finished move m - 1: that snapshot then holds no game of move m, and the
-// lanes stay within two moves of each other (the cache eviction bound, az_tree.h).
+// lanes stay within two moves of each other (the cache eviction bound, az_engine.hip).
 struct MoveClock {
   int32_t* arrive = nullptr;                // device [4]: lanes done with move m, slot m % 4
   unsigned long long* snap_host = nullptr;  // [4] pinned coherent, move m in slot m % 4
@@ -184,8 +215,7 @@ struct MoveClock {
 // for the caller's own fields), the cache control words, the slots holding a
 // game.  Clears *st first.
 inline int read_common_stats(az_stats* st, unsigned long long (&h)[kStatCount], const unsigned long long* stats,
-                             const int64_t* game_id, int slots, const unsigned long long* cache_ctl,
-                             unsigned long long cache_gen_size, uint32_t cache_mask) {
+                             const int64_t* game_id, int slots, const CacheCore& cache) {
   AZ_HIP(hipMemcpy(h, stats, sizeof(h), hipMemcpyDeviceToHost));
   std::vector<int64_t> gid(slots);
   AZ_HIP(hipMemcpy(gid.data(), game_id, gid.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
@@ -199,14 +229,14 @@ inline int read_common_stats(az_stats* st, unsigned long long (&h)[kStatCount], 
   st->cache_hits = (int64_t)h[kStatCacheHits];
   st->evaluations = (int64_t)h[kStatNNEvals];
   st->active_slots = std::count_if(gid.begin(), gid.end(), [](int64_t v) { return v >= 0; });
-  if (cache_ctl) {
+  if (cache.ctl) {
     unsigned long long ctl[3];
-    AZ_HIP(hipMemcpy(ctl, cache_ctl, sizeof(ctl), hipMemcpyDeviceToHost));
+    AZ_HIP(hipMemcpy(ctl, cache.ctl, sizeof(ctl), hipMemcpyDeviceToHost));
     st->cache_generation = (int64_t)ctl[0];
     st->cache_inserts = (int64_t)ctl[1];
-    st->cache_gen_size = (int64_t)cache_gen_size;
+    st->cache_gen_size = (int64_t)cache.gen_size;
     st->cache_entries = (int64_t)ctl[2];
-    st->cache_capacity = (int64_t)cache_mask + 1;
+    st->cache_capacity = (int64_t)cache.mask + 1;
   }
   return 0;
 }

@@ -1,5 +1,6 @@
 // az_tree.h -- device-resident MCTS forest: one tree per game slot.
 #pragma once
+#include "az_cache.h"
 #include "az_device.h"
 
 namespace az {
@@ -116,61 +117,9 @@ struct TreeDev {
   int32_t noise_rows;
 };
 
-// Transposition cache = the reference's plays_inferences (mcts/mcts.py:122-143,
-// utils.py:38-39): board -> (probs[A], value), shared by every game on the
-// device, cleared when the weights change.  Set-associative: a board hashes
-// to one bucket of kCacheBucket slots (its state words are one 64-B segment,
-// read in one round trip); inserts take the bucket's first reusable slot and
-// are dropped when every slot is live.  (Round 2 probed linearly across the
-// table: once stale entries had filled it, a miss walked max_probe = 32
-// acquire loads one after another, and games/s fell the longer a run went.)
-// The evaluator is deterministic per board, so hits never change a search.
-//
-// Eviction: least recently used, by generations (the reference's dict grows
-// without bound until the next model; a fixed table keeps what it can).
-// Every Ready entry is live -- a lookup accepts any of them, so the whole
-// table serves as plays_inferences.  Each `gen_size` inserts start a new
-// generation; a hit on an entry of an older generation moves it into the
-// current one (one CAS per entry per generation), so an entry's generation
-// is when it was last used.  An insert takes the bucket's first empty slot,
-// else its least recently used entry at least kCacheEvictAge generations old
-// (dropped when every entry is younger: a bucket of boards all in use).
-//
-// Overwrite safety: select finds an entry and expand reads its payload one
-// launch later.  Every hit leaves select stamped with the reader's generation
-// G (an older entry's refresh CAS must win; when it loses, the slot may be
-// being overwritten and the board counts as a miss).  The engine enables
-// eviction only when gen_size exceeds three moves of every slot's inserts
-// (slots * sims * 3: the lane drift is bounded to two moves by move events,
-// az_engine.hip), so at most one generation turn falls inside a reader's
-// window, an insert sees the entry at most 1 generation old, and
-// kCacheEvictAge = 2 keeps it.
-//
-// State word: [31:16] 16-bit fingerprint (hash bits 48-63, so most probes
-// need no key read), [15:2] generation mod 2^14, [1:0] status.
-enum : uint32_t { kCacheEmpty = 0, kCacheClaimed = 1, kCacheReady = 2 };
-constexpr uint32_t kCacheGenMask = 0x3fff;
-constexpr uint32_t kCacheGenDiv = 16;   // a generation = capacity / kCacheGenDiv inserts
-constexpr uint32_t kCacheEvictAge = 2;  // an insert may overwrite entries this many generations old
-AZ_HD uint32_t cache_fp(uint64_t h) { return (uint32_t)(h >> 48); }
-AZ_HD uint32_t cache_age(uint32_t st, uint32_t gen) { return (gen - (st >> 2)) & kCacheGenMask; }
-AZ_HD uint32_t cache_word(uint32_t fp, uint32_t gen, uint32_t status) {
-  return (fp << 16) | ((gen & kCacheGenMask) << 2) | status;
-}
-struct CacheDev {
-  Board* keys = nullptr;       // [cap]
-  uint32_t* state = nullptr;   // [cap]
-  float* pay = nullptr;        // [cap][A+1]: probs then value
-  uint32_t mask = 0;           // cap - 1
-  int enabled = 0;
-  unsigned long long* ctl = nullptr;  // device [0] generation, [1] inserts since the last clear,
-                                      // [2] of them into empty slots (= entries held)
-  unsigned long long gen_size = 0;    // inserts per generation; 0 = no eviction
-};
-constexpr int kCacheBucket = 16;  // slots per bucket (cache_log2 >= 4)
-AZ_HD uint32_t cache_bucket(uint32_t mask, uint64_t h) {  // mask = cap - 1: the bucket's first slot
-  return (uint32_t)h & mask & ~(uint32_t)(kCacheBucket - 1);
-}
+// The transposition cache (az_cache.h) keyed by boards; a payload is [A+1]
+// floats: probs then value.
+using CacheDev = Cache<Board>;
 
 // Self-play sample sink, indexed by game id - first_game.
 struct SampleDev {
@@ -208,8 +157,8 @@ void launch_compact(const GameCfg& g, const TreeDev& t, hipStream_t s);
 // games-finished count into *snap (pinned host memory) and resets *arrive
 void launch_move_end(int32_t* arrive, int n_lanes, const unsigned long long* done_count,
                      unsigned long long* snap, hipStream_t s);
-// cache on: misses are deduplicated inside select (step tag table); this
-// resolves the ones whose tag matched, by full-board compare
+// the synthetic evaluator on the queued boards (cache on: the misses' rows,
+// one per missing slot -- two slots that miss on one board each take a row)
 void launch_synth_eval(const GameCfg& g, const Board* boards, const int32_t* count, float* probs,
                        float* values, hipStream_t s);
 void launch_expand(const GameCfg& g, const TreeDev& t, const CacheDev& c, const float* probs,

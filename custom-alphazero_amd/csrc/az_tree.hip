@@ -168,19 +168,11 @@ __device__ void leaf_tail(const GameCfg& g, const TreeDev& t, const CacheDev& c,
   // the cache bucket's state words are requested before the queue claim's
   // atomic, so the two round trips overlap
   const uint64_t h = board_hash(b);
-  uint32_t gen = 0, fp = 0, base = 0;
-  uint32_t w[kCacheBucket];
+  CacheBucket bk;
   const uint64_t tag = (uint64_t)t.leaf_epoch << 32;
   t.leaf_board[s] = b;
   t.path_len[s] = depth;
-  if (c.enabled) {
-    gen = (uint32_t)__hip_atomic_load(c.ctl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    fp = cache_fp(h);
-    base = cache_bucket(c.mask, h);
-#pragma unroll
-    for (int k = 0; k < kCacheBucket; ++k)
-      w[k] = __hip_atomic_load(c.state + base + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  if (c.enabled) bk = cache_load(c, h);
   AZ_SEL_STAMP(s, 4);
   if (!c.enabled) {  // every leaf evaluated: its queue position is its row
     const int q = wave_claim(t.eval_count);
@@ -189,65 +181,16 @@ __device__ void leaf_tail(const GameCfg& g, const TreeDev& t, const CacheDev& c,
     wave_stat(t, kStatNNEvals);
     return;
   }
-  // repr(board) in plays_inferences (mcts.py:123).  Entries may be published
-  // concurrently by another lane's insert kernel: the acquire load pairs with
-  // its release exchange, so a Ready entry's key and payload are complete
-  // (a Claimed one reads as absent: the leaf is evaluated here, same result).
-  // Every Ready entry is live (LRU eviction, az_tree.h).
-  {
-    // the board's bucket: kCacheBucket state words (one 64-B segment) read
-    // at once with relaxed loads (above), scanned in registers; a candidate's
-    // key is read after an acquire fence (pairs with the insert's release)
-    int hit = -1;
-    uint32_t hst = 0;
-    // the fingerprint matches (inserts fill a bucket in slot order: nothing
-    // past an empty slot), then ONE acquire for the wave -- a fence per
-    // candidate position had the wave invalidating its CU's L1 (the tower
-    // tiles' weight fragments too) up to 16 times -- then the keys in order
-    uint32_t cm = 0;
-    bool stop = false;
-#pragma unroll
-    for (int k = 0; k < kCacheBucket; ++k) {
-      const uint32_t st = w[k];
-      if (stop) continue;
-      if (st == kCacheEmpty) stop = true;
-      else if ((st & 3u) == kCacheReady && (st >> 16) == fp) cm |= 1u << k;
-    }
-    if (cm) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      for (; cm; cm &= cm - 1) {
-        const int k = __builtin_ctz(cm);
-        if (same_board(c.keys[base + k], b)) {
-          hit = k;
-#pragma unroll
-          for (int kk = 0; kk < kCacheBucket; ++kk)
-            if (kk == k) hst = w[kk];  // (constant indices: w stays in VGPRs)
-          break;
-        }
-      }
-    }
-    bool use = hit >= 0;
-    if (use && cache_age(hst, gen) != 0) {
-      // a hit on an older generation moves the entry into the current one
-      // (its last use: inserts evict the least recently used), at most one CAS
-      // per entry per generation.  The CAS must win -- or find the entry
-      // already moved by another reader and still this board -- else an insert
-      // may be overwriting the slot and the board counts as a miss (az_tree.h)
-      const uint32_t want = cache_word(fp, gen, kCacheReady);
-      const uint32_t prev = atomicCAS(c.state + base + hit, hst, want);
-      if (prev != hst) {
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        use = prev == want && same_board(c.keys[base + hit], b);
-      }
-    }
-    if (use) {
-      const uint32_t idx = base + hit;
-      t.leaf_src[s] = tag | idx;
-      AZ_SEL_STAMP(s, 5);
-      AZ_SEL_VALUE(s, 7, depth | (1 << 16) | ((uint64_t)s << 32));
-      wave_stat(t, kStatCacheHits);
-      return;
-    }
+  // repr(board) in plays_inferences (mcts.py:123): the bucket read above,
+  // looked up per thread (az_cache.h; a Claimed entry reads as absent: the
+  // leaf is evaluated here, same result)
+  const int idx = cache_lookup(c, bk, [&](uint32_t i) { return same_board(c.keys[i], b); });
+  if (idx >= 0) {
+    t.leaf_src[s] = tag | (uint32_t)idx;
+    AZ_SEL_STAMP(s, 5);
+    AZ_SEL_VALUE(s, 7, depth | (1 << 16) | ((uint64_t)s << 32));
+    wave_stat(t, kStatCacheHits);
+    return;
   }
   AZ_SEL_STAMP(s, 5);
   AZ_SEL_VALUE(s, 7, depth | (2 << 16) | ((uint64_t)s << 32));
@@ -577,10 +520,11 @@ __global__ __launch_bounds__(kGameBlock) void select_group_kernel(GameCfg g, Tre
 }
 
 // ------------------------------------------------------------ cache insert
-// plays_inferences[repr(board)] = probabilities, value (mcts.py:142): one
-// writer per distinct board (dedup), racing only for the bucket's first empty
-// slot or its least recently used entry kCacheEvictAge+ generations old
-// (az_tree.h); a lost race moves on to the next candidate.
+// plays_inferences[repr(board)] = probabilities, value (mcts.py:142), one
+// insert per evaluator row: two slots that miss on one board in one
+// simulation each took a row and each insert (a bucket may then hold the
+// board twice; a lookup takes the first).  The writers race only for the
+// claim (az_cache.h).
 // Called by every thread of an insert block (u: the thread's evaluator row;
 // past the rows, no entry).  The entries' keys and payloads are published
 // behind ONE release per block (every wave's stores drained, a barrier, lane
@@ -590,51 +534,18 @@ __device__ void cache_insert_row(const GameCfg& g, const TreeDev& t, const Cache
                                  const float* __restrict__ probs, const float* __restrict__ values, int u) {
   const int rows = *t.nn_count;
   if ((u - (int)threadIdx.x) >= rows) return;  // block-uniform: the whole block past the rows
-  int idx = -1;
+  CacheClaim cl{-1, false};
   uint32_t word = 0;
-  bool was_empty = false;
   if (u < rows) {
     const Board b = t.nn_board[u];
-    const uint64_t h = board_hash(b);
-    const uint32_t gen = (uint32_t)__hip_atomic_load(c.ctl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const uint32_t fp = cache_fp(h);
-    const uint32_t base = cache_bucket(c.mask, h);
-    uint32_t w[kCacheBucket];
-#pragma unroll
-    for (int k = 0; k < kCacheBucket; ++k)
-      w[k] = __hip_atomic_load(c.state + base + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    uint32_t tried = 0;  // slots whose CAS lost (claimed or refreshed meanwhile)
-    for (int attempt = 0; attempt < kCacheBucket && idx < 0; ++attempt) {
-      // candidate: the first empty slot, else the oldest evictable entry (the
-      // first of equal ages); scanned with constant indices (w stays in VGPRs)
-      int pick = -1;
-      uint32_t pst = 0, page = 0;
-      bool pempty = false;
-#pragma unroll
-      for (int k = 0; k < kCacheBucket; ++k) {
-        const uint32_t st = w[k];
-        if (pempty || ((tried >> k) & 1u)) continue;
-        if (st == kCacheEmpty) {
-          pick = k, pst = st, pempty = true;
-        } else if (c.gen_size) {
-          const uint32_t age = cache_age(st, gen);
-          if (age >= kCacheEvictAge && age > page) pick = k, pst = st, page = age;
-        }
-      }
-      if (pick < 0) break;  // every entry of the bucket is in use: evaluated again when met
-      if (atomicCAS(c.state + base + pick, pst, cache_word(fp, gen, kCacheClaimed)) == pst) {
-        idx = (int)(base + pick);
-        was_empty = pempty;
-      } else {
-        tried |= 1u << pick;
-      }
-    }
-    if (idx >= 0) {
-      c.keys[idx] = b;
-      float* dst = c.pay + (size_t)idx * (g.A + 1);
+    const CacheBucket bk = cache_load(c, board_hash(b));
+    cl = cache_claim(c, bk);
+    if (cl.idx >= 0) {
+      c.keys[cl.idx] = b;
+      float* dst = c.pay + (size_t)cl.idx * (g.A + 1);
       for (int a = 0; a < g.A; ++a) dst[a] = probs[(size_t)u * g.A + a];
       dst[g.A] = values[u];
-      word = cache_word(fp, gen, kCacheReady);
+      word = cache_word(bk.fp, bk.gen, kCacheReady);  // the claim-time generation
     }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -644,13 +555,11 @@ __device__ void cache_insert_row(const GameCfg& g, const TreeDev& t, const Cache
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
   __syncthreads();
-  if (idx < 0) return;
-  atomicExch(c.state + idx, word);
+  if (cl.idx < 0) return;
+  atomicExch(c.state + cl.idx, word);
   wave_stat(t, kStatCacheInserts);
-  if (was_empty) wave_claim64(c.ctl + 2);
-  // every gen_size-th insert since the clear opens a new generation
-  const unsigned long long n = wave_claim64(c.ctl + 1) + 1;
-  if (c.gen_size && n % c.gen_size == 0) atomicAdd(c.ctl, 1ull);
+  if (cl.was_empty) wave_claim64(c.ctl + 2);
+  cache_turn(c, wave_claim64(c.ctl + 1) + 1);
 }
 
 // ------------------------------------------------------ synthetic evaluator
@@ -670,7 +579,7 @@ __global__ __launch_bounds__(256) void synth_eval_kernel(GameCfg g, const Board*
 // boards to the cache (blocks from exp_blocks on, one nn row per thread):
 // the entries the leaves expanded here read were stamped with the current
 // generation by select, which an insert never evicts (kCacheEvictAge,
-// az_tree.h), so the two halves are independent and share one launch.
+// az_cache.h), so the two halves are independent and share one launch.
 // SHAPE 1 (Connect-4, 6x7, n = 4, gravity): the legal columns are the top
 // row's empty cells, in action order = moves order, and fewer than 8 of them,
 // so normalize's numpy sum is the plain left-to-right one -- no cell scans.
