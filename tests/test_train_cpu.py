@@ -190,3 +190,19 @@ def test_train_kernels_build_without_spills(tmp_path):
     assert len(fwd) == 2 and len(dgrad) == 3 and len(wgrad) == 2, spills
     assert fwd == [0, 0] and dgrad == [0, 0, 0] and wgrad == [0, 0], spills
     assert all(v == 0 for v in spills.values()), spills
+
+
+def test_bn_epsilon_case_meets_the_input_condition():
+    """test_train_shapes_gpu.test_bn_epsilon_reaches_the_kernels' input (6x7, n 5, depth 1, eps 1e-5),
+    without a GPU: every tensor's e32 <= KINK_FREE, ReLU margin >= 0.95 x CLEAR_MARGIN, and the
+    eps = 1e-3 gradient on the same weights 100 tolerances or more away."""
+    hyper = dict(lr=1e-2, momentum=0.9, l2=1e-4, bn_momentum=0.99)
+    ref = R.reference_run(6, 7, True, 5, 1, eps=1e-5, **hyper)
+    assert R.reference_run(6, 7, True, 5, 1, **hyper) is R.reference_run(6, 7, True, 5, 1, eps=1e-3, **hyper)
+    g64, g32 = ref["f64"][0]["grad"], ref["f32"][0]["grad"]
+    names = [k for k in g64 if R.conv_bias_unit(k) is None]
+    assert all(R.rel_l2(g32[k], g64[k]) <= R.KINK_FREE for k in names)
+    assert ref["f64"][0]["relu_margin"] >= 0.95 * R.CLEAR_MARGIN
+    other = R.RefTrainer(ref["spec"], ref["weights"], 1, torch.float64, eps=1e-3)
+    other.step(*ref["batch"], **hyper)
+    assert max(R.rel_l2(other.grad[k].numpy(), g64[k]) / R.tolerance(R.rel_l2(g32[k], g64[k])) for k in names) >= 100

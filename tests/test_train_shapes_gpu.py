@@ -9,8 +9,9 @@ entries in heads_kernel, the odd-HW tail of wgrad_mfma_kernel's cell pairs),
 parts with ragged row parts, value_hidden 1 / 300 / 1024, depth 8 and 16,
 one-board batches, policy logits scaled until the 1e-7 inside the log carries
 the gradient, targets with exact zeros, channels with zero variance, a
-saturated value head, state carried from one step into the next, and the
-update's arithmetic against the device's own gradient.
+saturated value head, a bn_epsilon other than the default, state carried from
+one step into the next, and the update's arithmetic against the device's own
+gradient.
 
 Tolerance: train_ref.tolerance, as in test_train_gpu.py (8 x e32, floor 1e-6,
 cap 1e-4; e32 from the CPU's float32 run, never from the device).  Every parity
@@ -41,6 +42,7 @@ tensor, one step), the tensor closest to its bound, and the losses' errors
   n 5, dead channels       8.9e-7   policy.conv.gamma 3.4e-7 of 1.4e-6   2.8e-8 / 2.5e-8 / 6.4e-8
                            (moving statistics 4.0e-7, the dead channels' variance 4.2e-8)
   n 5, saturated value     1.2e-6   policy.conv.gamma 4.3e-7 of 1.0e-6   8.3e-8 / 7.5e-8 / 1.4e-7
+  n 5, bn_epsilon 1e-5     8.4e-7   stem.beta 7.6e-7 of 6.2e-6           2.6e-8 / 2.1e-8 / 3.4e-8
   train() on 4, 4, 1       loss 5.0e-8 (e32 1.0e-7)
   l2 = 0.5 against l2 = 0  the total moves by 0.5 sum ||W||^2 within 1.4e-8
 Every tensor above a third of its bound sits at the bound's floor of 1e-6 (its
@@ -72,9 +74,10 @@ pytestmark = pytest.mark.gpu
 HYPER = dict(lr=1e-2, momentum=0.9, l2=1e-4, bn_momentum=0.99)
 
 
-def _reference(shape, hidden=256, weights_mod=None, batch_mod=None, gradients=True):
+def _reference(shape, hidden=256, weights_mod=None, batch_mod=None, gradients=True, eps=1e-3):
     """The shared CPU runs of one step, after the condition on the inputs."""
-    ref = R.reference_run(*shape, steps=1, hidden=hidden, weights_mod=weights_mod, batch_mod=batch_mod, **HYPER)
+    ref = R.reference_run(*shape, steps=1, hidden=hidden, weights_mod=weights_mod, batch_mod=batch_mod, eps=eps,
+                          **HYPER)
     g64, g32 = ref["f64"][0]["grad"], ref["f32"][0]["grad"]
     if gradients:
         for k in g64:
@@ -84,9 +87,9 @@ def _reference(shape, hidden=256, weights_mod=None, batch_mod=None, gradients=Tr
     return ref
 
 
-def _trainer(shape, weights, hidden=256, max_batch=None):
+def _trainer(shape, weights, hidden=256, max_batch=None, eps=1e-3):
     H, W, gravity, n, depth = shape
-    tr = az.Trainer(H, W, gravity, max_batch=max_batch or n, depth=depth, value_hidden=hidden)
+    tr = az.Trainer(H, W, gravity, max_batch=max_batch or n, depth=depth, value_hidden=hidden, bn_epsilon=eps)
     tr.set_weights(weights.items())
     return tr
 
@@ -113,12 +116,13 @@ def _check_losses(losses, ref, shape):
         assert err <= R.tolerance(e32), (name, losses[i], l64)
 
 
-def _one_step(shape, hidden=256, weights_mod=None, batch_mod=None, tag=""):
+def _one_step(shape, hidden=256, weights_mod=None, batch_mod=None, tag="", eps=1e-3):
     """One step on the device against the reference: the checks of
-    test_train_gpu.test_one_step_gradients_and_losses.  Returns (ref, the
-    device's weights after the step)."""
-    ref = _reference(shape, hidden, weights_mod, batch_mod)
-    tr = _trainer(shape, ref["weights"], hidden)
+    test_train_gpu.test_one_step_gradients_and_losses.  `eps` is the reference's
+    and the trainer's bn_epsilon.  Returns (ref, the device's weights after the
+    step)."""
+    ref = _reference(shape, hidden, weights_mod, batch_mod, eps=eps)
+    tr = _trainer(shape, ref["weights"], hidden, eps=eps)
     losses = tr.step(*ref["batch"], **HYPER)
     dev, w1 = tr.read_all(az.TRAIN_GRAD), tr.read_all(az.TRAIN_WEIGHT)
     tr.close()
@@ -289,6 +293,25 @@ def test_saturated_value_head():
         _, v, _ = R.forward_train(w, torch.tensor(ref["batch"][0], dtype=torch.float64), shape[4])
     print(f"saturated value head: max |v| {float(v.abs().max()):.4f}")
     assert float(v.abs().max()) >= 0.99
+
+
+def test_bn_epsilon_reaches_the_kernels():
+    """bn_epsilon = 1e-5 (every other test of this trainer runs the default,
+    1e-3).  On the CPU alone, the float64 gradient on the same weights and batch
+    with eps = 1e-3 is 6.4e-4 (value.dense2.bias) to 2.1e-1 (value.conv.beta)
+    from the eps = 1e-5 gradient, 640 tolerances at least: a trainer that
+    ignored the field fails on every tensor; one at 100 tolerances is asserted."""
+    shape, eps = (6, 7, True, 5, 1), 1e-5
+    ref = _reference(shape, eps=eps)
+    g64, g32 = ref["f64"][0]["grad"], ref["f32"][0]["grad"]
+    other = R.RefTrainer(ref["spec"], ref["weights"], shape[4], torch.float64, eps=1e-3)
+    other.step(*ref["batch"], **HYPER)
+    ratio = {k: R.rel_l2(other.grad[k].numpy(), g64[k]) / R.tolerance(R.rel_l2(g32[k], g64[k]))
+             for k in g64 if R.conv_bias_unit(k) is None}
+    print(f"bn_epsilon 1e-5: the eps = 1e-3 gradient is {min(ratio.values()):.0f} to {max(ratio.values()):.0f} "
+          "tolerances away")
+    assert max(ratio.values()) >= 100
+    _one_step(shape, tag="bn_epsilon 1e-5", eps=eps)
 
 
 # ---------------------------------------------------------------- 4. no state leaks between steps

@@ -204,7 +204,7 @@ _CACHE = {}
 
 
 def reference_run(H, W, gravity, n, depth, steps=1, lr=1e-2, momentum=0.9, l2=1e-4, bn_momentum=0.99, seed=0,
-                  hidden=256, weights_mod=None, batch_mod=None):
+                  hidden=256, weights_mod=None, batch_mod=None, eps=1e-3):
     """Float64 and float32 CPU runs of `steps` steps on one fixed batch, computed
     once per shape and shared (callers must not modify the result).  `seed`
     draws the weights, which clear_kinks then moves clear of every ReLU kink of
@@ -212,9 +212,10 @@ def reference_run(H, W, gravity, n, depth, steps=1, lr=1e-2, momentum=0.9, l2=1e
     is the value head's width.  `weights_mod(weights) -> weights` and
     `batch_mod((x, pi, z)) -> (x, pi, z)` are module-level functions (they are
     part of the cache key) that reshape the drawn inputs before clear_kinks
-    sees them.  Returns a dict: spec, weights, batch, and per dtype key ('f64',
+    sees them.  `eps` is the BatchNormalization epsilon of clear_kinks and of
+    both runs.  Returns a dict: spec, weights, batch, and per dtype key ('f64',
     'f32') the list of per-step records {losses, grad, mom, w, relu_margin}."""
-    key = (H, W, gravity, n, depth, steps, lr, momentum, l2, bn_momentum, seed, hidden, weights_mod, batch_mod)
+    key = (H, W, gravity, n, depth, steps, lr, momentum, l2, bn_momentum, seed, hidden, weights_mod, batch_mod, eps)
     if key in _CACHE:
         return _CACHE[key]
     spec = make_spec(H, W, gravity, depth, hidden=hidden)
@@ -224,10 +225,10 @@ def reference_run(H, W, gravity, n, depth, steps=1, lr=1e-2, momentum=0.9, l2=1e
         weights = weights_mod({k: np.array(v, np.float32) for k, v in weights.items()})
     if batch_mod is not None:
         batch = tuple(np.ascontiguousarray(a, np.float32) for a in batch_mod(tuple(a.copy() for a in batch)))
-    weights = clear_kinks(weights, batch[0], depth)
+    weights = clear_kinks(weights, batch[0], depth, eps=eps)
     out = {"spec": spec, "weights": weights, "batch": batch}
     for tag, dt in (("f64", torch.float64), ("f32", torch.float32)):
-        ref = RefTrainer(spec, weights, depth, dt)
+        ref = RefTrainer(spec, weights, depth, dt, eps)
         recs = []
         for _ in range(steps):
             losses = ref.step(*batch, lr, momentum, l2, bn_momentum)
