@@ -171,10 +171,11 @@ def restate(w, x, depth, dtype=np.float64, **mutation):
     return heads(w, trunk(w, x, depth, dtype, **mutation), dtype)
 
 
-def _lively(H, W, gravity, depth, hidden, x, seed):
-    A = W if gravity else H * W
-    w = {k: np.asarray(v, np.float64) for k, v in
-         init_weights(weight_spec(H, W, A, depth=depth, hidden=hidden), seed=seed, randomize_bn=True).items()}
+def _lively(H, W, gravity, depth, hidden, x, seed, in_channels=4, A=None):
+    """A: the action space where it is not the board's own (chess, tests/chess_forward_ref.py)."""
+    A = A if A is not None else W if gravity else H * W
+    spec = weight_spec(H, W, A, depth=depth, hidden=hidden, in_channels=in_channels)
+    w = {k: np.asarray(v, np.float64) for k, v in init_weights(spec, seed=seed, randomize_bn=True).items()}
     w["value.conv.beta"] = np.full_like(w["value.conv.beta"], 0.5)
     w["policy.conv.beta"] = np.full_like(w["policy.conv.beta"], 0.3)
     h = trunk(w, x, depth)  # the trunk stays Keras init

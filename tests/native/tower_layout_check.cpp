@@ -9,6 +9,10 @@
 // or HW; depth 1, 4, 16; hidden 1, 64, 255, 256), each chosen layout checked
 // against the library's other tower16_* functions ->
 // {"shapes", "not_ok": [shapes without a layout], "failures": [shape + what]}.
+// --rows-stem, then groups of depth hidden: the chess network's input-row form
+// (H = W = 8, A = 1880) -> per group tower, tile_rows, boards, dbuf, the staged
+// prefix, the LDS bytes of the chosen form and of the in-place one, and the
+// issued FLOP per board with 2 (self-play) and with 4 stem chunks.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -84,12 +88,47 @@ int sweep() {
   printf("{\"shapes\": %d, \"not_ok\": [%s], \"failures\": [%s]}\n", shapes, not_ok.c_str(), failures.c_str());
   return 0;
 }
+
+// the chess network's layout (TowerShape::rows_stem, H = W = 8, A = 1880): the heads' dense layers run in
+// kernels of their own, so the staged prefix ends before bpd and tower16_heads_fit does not apply
+int rows_stem(int argc, char** argv) {
+  printf("[");
+  for (int a = 2; a + 1 < argc; a += 2) {
+    az::TowerShape s;
+    s.H = s.W = 8, s.A = 1880, s.depth = atoi(argv[a]), s.hidden = atoi(argv[a + 1]), s.cus = 256, s.lanes = 1;
+    s.rows_stem = true;
+    const TowerLayout L = az::tower16_choose_layout(s);
+    printf("%s{\"depth\": %d, \"hidden\": %d, \"tower\": %d", a > 2 ? ",\n" : "", s.depth, s.hidden, (int)L.ok);
+    if (L.ok) {
+      const TowerTiles& t = L.main;
+      const int k = __builtin_popcount(t.skip[0]) + __builtin_popcount(t.skip[1]);
+      printf(", \"tile_rows\": %d, \"boards\": %d, \"dbuf\": %d, \"staged\": %d, \"off_bpd\": %d, \"lds_bytes\": %zu, "
+             "\"lds_bytes_in_place\": %zu, \"dual\": %d, \"skipped\": %d, \"flop\": %.17g, \"flop_chunks2\": %.17g, "
+             "\"flop_chunks4\": %.17g",
+             t.rows, az::tower16_boards_per_tile(64, t.rows), (int)L.dbuf, t.staged_floats, L.blob.off_bpd,
+             az::tower16_lds_bytes(64, t.rows, t.staged_floats, L.dbuf),
+             az::tower16_lds_bytes(64, t.rows, t.staged_floats, false), (int)(L.alt.rows != 0), k,
+             t.issued_flop_per_board, az::tower16_issued_flop_per_board(64, t.rows, s.depth, t.skip, true, 2),
+             az::tower16_issued_flop_per_board(64, t.rows, s.depth, t.skip, true, 4));
+    }
+    printf("}");
+  }
+  printf("]\n");
+  return 0;
+}
 }  // namespace
 
 int main(int argc, char** argv) {
   if (argc == 2 && !strcmp(argv[1], "--sweep")) return sweep();
+  if (argc >= 2 && !strcmp(argv[1], "--rows-stem")) {
+    if (argc % 2) {
+      fprintf(stderr, "usage: tower_layout_check --rows-stem (depth hidden)...\n");
+      return 2;
+    }
+    return rows_stem(argc, argv);
+  }
   if ((argc - 1) % 5) {
-    fprintf(stderr, "usage: tower_layout_check (H W A depth hidden)... | --sweep\n");
+    fprintf(stderr, "usage: tower_layout_check (H W A depth hidden)... | --sweep | --rows-stem (depth hidden)...\n");
     return 2;
   }
   printf("[");
