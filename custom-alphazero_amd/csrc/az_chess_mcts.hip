@@ -714,8 +714,7 @@ __device__ __forceinline__ void select_slot(const CCfg& g, const CTree& t, const
       return;
     }
     const double sq = t.powtab[sum];
-    double best_v = -INFINITY;
-    int best = 1 << 30;
+    az::SelectBest sel = az::select_none();  // a lane without an edge ranks below every edge
     if (NOISE && depth == 0) {  // (a constant false without NOISE: none of this is compiled in)
       NoiseSmem& sm = *nsm;
       bool drawn = cnt <= AZ_CHESS_MAX_MOVES;
@@ -748,43 +747,21 @@ __device__ __forceinline__ void select_slot(const CCfg& g, const CTree& t, const
         const double prior = kept + g.noise_ratio * sm.d[j];
         const double qv = e.N ? e.W / (double)e.N : 0.0;
         const double u = g.c_puct * prior * sq / (double)(1 + e.N);
-        const double v = qv + u;
-        if (best == 1 << 30 || az::argmax_before(v, j, best_v, best)) {
-          best_v = v;
-          best = j;
-        }
-      }
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) {
-        const double ov = __shfl_xor(best_v, off, 64);
-        const int oj = __shfl_xor(best, off, 64);
-        // a lane without an edge (1 << 30) ranks below every edge
-        if (oj != 1 << 30 && (best == 1 << 30 || az::argmax_before(ov, oj, best_v, best))) {
-          best_v = ov;
-          best = oj;
-        }
+        sel = az::select_edge(sel, qv + u, j);
       }
     } else {
       for (int j = lane; j < cnt; j += 64) {
         const Edge e = E[first + j];
         const double qv = e.N ? e.W / (double)e.N : 0.0;
         const double u = g.c_puct * e.prior * sq / (double)(1 + e.N);
-        const double v = qv + u;
-        if (v > best_v) {  // within a lane j increases: strict > keeps the first
-          best_v = v;
-          best = j;
-        }
-      }
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) {
-        const double ov = __shfl_xor(best_v, off, 64);
-        const int oj = __shfl_xor(best, off, 64);
-        if (ov > best_v || (ov == best_v && oj < best)) {  // np.argmax: first maximum
-          best_v = ov;
-          best = oj;
-        }
+        sel = az::select_edge(sel, qv + u, j);
       }
     }
+    // np.argmax over the node's edges (az_device.h): wave-uniform and < cnt
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+      sel = az::select_merge(sel, (int64_t)__shfl_xor((long long)sel.key, off, 64), __shfl_xor(sel.idx, off, 64));
+    const int best = sel.idx;
     if (depth >= g.max_depth) {
       if (lane == 0) flag(t, az::kErrPath);
       return;

@@ -309,12 +309,44 @@ AZ_HD T pairwise_sum(const T* a, int n) {
   return pairwise_block(a, n);
 }
 
-// np.argmax order: NaN above every number, then value, then the lower index
-AZ_HD bool argmax_before(double v, int i, double bv, int bi) {
-  if (bv != bv) return v != v && i < bi;
-  if (v != v) return true;
-  return v > bv || (v == bv && i < bi);
+// ------------------------------------------------------- the best-edge choice
+// get_best_edge (mcts.py:64-68) is np.argmax over the edges' UCBs: the first
+// NaN wins; else the first maximum, -0.0 == +0.0 a tie, +-inf ordinary
+// numbers.  Stated once for every descent of both engines (serial loop, group
+// reduction, wave reduction; with and without root noise): a UCB is mapped
+// once, where it is computed, to an integer key that sorts as np.argmax ranks
+// -- NaN above +inf, -0.0 folded onto +0.0, negative numbers below it in
+// value order -- and the running best is (key, index) under "greater key,
+// then lower index".  That is a total order over edges (indices are
+// distinct), so a reduction's merge is commutative and associative: every
+// lane of a group ends with the same pair, whatever the partner steps.  "No
+// edge" (a lane past the node's count, a loop before its first edge) is
+// (kSelectNoEdge, 0): below every key an edge can have, -inf and NaN
+// included, so the index comes from an edge whenever one exists and is 0 --
+// still below any count >= 1 -- when none does.  A step costs what the plain
+// first-maximum step cost (one greater, one equal, one less compare, two
+// selects), on integers; the NaN and zero handling is paid once per edge.
+constexpr int64_t kSelectNoEdge = INT64_MIN;
+AZ_HD int64_t select_key(double v) {
+  int64_t b = __builtin_bit_cast(int64_t, v);
+  const int64_t flipped = b ^ INT64_MAX;  // sign-magnitude -> two's complement order
+  b = b < 0 ? flipped : b;                // (-0.0 -> -1, raised to +0.0's 0 below)
+  b = b == -1 ? 0 : b;
+  return v != v ? INT64_MAX : b;
 }
+struct SelectBest {
+  int64_t key;
+  int idx;
+};
+AZ_HD SelectBest select_none() { return {kSelectNoEdge, 0}; }
+// (selects, not branches: `|` and `&` keep a reduction step free of exec masking)
+AZ_HD bool select_before(int64_t k, int i, int64_t bk, int bi) { return bool((k > bk) | ((k == bk) & (i < bi))); }
+// the per-lane update and the reduction's merge step: the better of the two
+AZ_HD SelectBest select_merge(SelectBest a, int64_t k, int i) {
+  const bool take = select_before(k, i, a.key, a.idx);
+  return {take ? k : a.key, take ? i : a.idx};
+}
+AZ_HD SelectBest select_edge(SelectBest a, double ucb, int i) { return select_merge(a, select_key(ucb), i); }
 
 // ------------------------------------------------------- synthetic evaluator
 // oracle/synth.py, restated: dyadic priors k/64 and values k/128, one board

@@ -247,8 +247,7 @@ __device__ __forceinline__ void select_body(const GameCfg& g, const TreeDev& t, 
       return;
     }
     const double sq = t.powtab[sum];
-    int best = 0;
-    double best_v = 0.0;
+    SelectBest sel = select_none();
     if (NOISE && depth == 0) {
       double gam[kMaxActions], acc = 0.0;
       const double* hn = nullptr;  // tree API: the host's normalised draw
@@ -271,28 +270,21 @@ __device__ __forceinline__ void select_body(const GameCfg& g, const TreeDev& t, 
         const Edge e = E[first + i];
         const double q = e.N ? e.W / (double)e.N : 0.0;
         const double u = g.c_puct * noisy_prior(g, e, hn ? hn[i] : gam[i] * invacc) * sq / (double)(1 + e.N);
-        const double ucb = q + u;
-        if (i == 0 || argmax_before(ucb, i, best_v, best)) {
-          best = i;
-          best_v = ucb;
-        }
+        sel = select_edge(sel, q + u, i);
       }
     } else {
       for (int i = 0; i < cnt; ++i) {
         const Edge e = E[first + i];
         const double q = e.N ? e.W / (double)e.N : 0.0;
         const double u = g.c_puct * e.prior * sq / (double)(1 + e.N);
-        const double ucb = q + u;
-        if (i == 0 || ucb > best_v) {
-          best = i;
-          best_v = ucb;
-        }
+        sel = select_edge(sel, q + u, i);
       }
     }
     if (depth >= g.max_depth) {
       flag_error(t, kErrPath);
       return;
     }
+    const int best = sel.idx;  // < cnt (az_device.h)
     const Edge& e = E[first + best];
     path[depth++] = first + best;
     status = play_bb(g, mk, b, e.action & kActMask);
@@ -329,24 +321,22 @@ template <int K>
 __device__ __forceinline__ double group_partner(double v) {
   return __hiloint2double(group_partner<K>(__double2hiint(v)), group_partner<K>(__double2loint(v)));
 }
+template <int K>
+__device__ __forceinline__ int64_t group_partner(int64_t v) {
+  const uint32_t hi = (uint32_t)group_partner<K>((int)(v >> 32)), lo = (uint32_t)group_partner<K>((int)v);
+  return (int64_t)(((uint64_t)hi << 32) | lo);
+}
 template <int L, int K = 0>
 __device__ __forceinline__ int group_sum(int v) {
   if constexpr ((1 << K) < L) return group_sum<L, K + 1>(v + group_partner<K>(v));
   else return v;
 }
-// first maximum of (v, i) over the group; NAN_MAX: in np.argmax's order
-// (argmax_before), else `>` with the lower index on ties
-template <int L, bool NAN_MAX, int K = 0>
-__device__ __forceinline__ void group_argmax(double& v, int& i) {
-  if constexpr ((1 << K) < L) {
-    const double ov = group_partner<K>(v);
-    const int oi = group_partner<K>(i);
-    // (selects, not branches: `|` and `&` keep the step free of exec masking)
-    const bool take = NAN_MAX ? argmax_before(ov, oi, v, i) : bool((ov > v) | ((ov == v) & (oi < i)));
-    v = take ? ov : v;
-    i = take ? oi : i;
-    group_argmax<L, NAN_MAX, K + 1>(v, i);
-  }
+// the group's best edge in np.argmax's order (select_merge, az_device.h):
+// every lane ends with the same pair
+template <int L, int K = 0>
+__device__ __forceinline__ SelectBest group_argmax(SelectBest a) {
+  if constexpr ((1 << K) < L) return group_argmax<L, K + 1>(select_merge(a, group_partner<K>(a.key), group_partner<K>(a.idx)));
+  else return a;
 }
 
 // Group descent: a game is a group of L lanes (L = next power of two >= A).
@@ -419,8 +409,7 @@ __device__ __forceinline__ void select_group_body(const GameCfg& g, const TreeDe
       sq = t.powtab[sum];
     }
     AZ_SEL_PHASE(ph_load);
-    double best_v = -INFINITY;
-    int best = L;
+    SelectBest sel = select_none();  // a lane past the node's edges
     if (NOISE && depth == 0) {
       double dj = 0.0;  // this lane's edge's noise component
       if (t.noise_in) {
@@ -454,19 +443,16 @@ __device__ __forceinline__ void select_group_body(const GameCfg& g, const TreeDe
       if (mine) {
         const double q = e.N ? e.W / (double)e.N : 0.0;
         const double u = g.c_puct * noisy_prior(g, e, dj) * sq / (double)(1 + e.N);
-        best_v = q + u;
-        best = j;
+        sel = select_edge(sel, q + u, j);
       }
-      group_argmax<L, true>(best_v, best);
     } else {
       if (mine) {
         const double q = e.N ? e.W / (double)e.N : 0.0;
         const double u = g.c_puct * e.prior * sq / (double)(1 + e.N);
-        best_v = q + u;
-        best = j;
+        sel = select_edge(sel, q + u, j);
       }
-      group_argmax<L, false>(best_v, best);  // np.argmax: first maximum
     }
+    const int best = group_argmax<L>(sel).idx;  // np.argmax; group-uniform and < cnt
     if (depth >= g.max_depth) {
       if (j == 0) flag_error(t, kErrPath);
       drain();

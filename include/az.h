@@ -195,7 +195,15 @@ int az_engine_set_weights(az_engine* eng, const az_tensor* tensors, int n);
  * az_tree_play then fail with AZ_E_STATE until az_selfplay_begin or
  * az_tree_reset).  Host buffers, valid during the call.
  * The outputs must be a deterministic function of the board (the cache
- * relies on it, as the reference's plays_inferences dict does). */
+ * relies on it, as the reference's plays_inferences dict does).
+ * They may be any float32, negative, subnormal and non-finite included:
+ * nothing is rejected or cleaned, as in the reference.  The search follows the
+ * reference's arithmetic on them (the float32 normalisation of
+ * normalize_probabilities, float64 UCB and backup: a NaN or inf reaches the
+ * priors and W as numpy would carry it) and takes the best edge in
+ * np.argmax's order (mcts.py:64-68): the first NaN, else the first maximum,
+ * -0.0 and +0.0 a tie.  A tree whose visits follow one NaN edge keeps more of
+ * itself after a move than a spread search: arena_edges may need raising. */
 typedef int32_t (*az_eval_fn)(void* user, const float* x, int32_t n, float* probs, float* values);
 int az_engine_set_evaluator(az_engine* eng, az_eval_fn fn, void* user);
 

@@ -175,7 +175,10 @@ int az_chess_engine_set_weights(az_chess_engine* eng, const az_tensor* tensors, 
  * az_chess_tree_reset.  Searching before a callback is set is AZ_E_STATE.
  * The outputs must be a deterministic function of x (the cache relies on it,
  * as the reference's plays_inferences dict does); results are identical with
- * the cache on or off.  az_chess_forward and az_chess_engine_set_weights on
+ * the cache on or off.  They may be any float32, non-finite included; nothing
+ * is rejected, as in the reference: the search follows the reference's
+ * arithmetic and np.argmax's order for the best edge, the first NaN first
+ * (az.h, az_eval_fn).  az_chess_forward and az_chess_engine_set_weights on
  * such an engine answer AZ_E_STATE.  Every simulation waits for its callback,
  * so az_chess_selfplay_step with st = NULL is effectively synchronous here. */
 int az_chess_engine_set_evaluator(az_chess_engine* eng, az_eval_fn fn, void* user);

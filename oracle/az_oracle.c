@@ -468,20 +468,31 @@ static int orc_new_node(orc_tree* t, const int8_t* board, int status) {
     return id;
 }
 
+/* np.argmax over a list of Python floats (get_best_edge, mcts.py:64-68): the
+ * first NaN wins; else the first maximum, with -0.0 == +0.0 a tie and +-inf
+ * ordinary numbers.  Every best-edge choice of both oracles goes through it;
+ * tests/test_select_order_cpu.py pins it against numpy itself. */
+int orc_argmax_f64(const double* v, int n) {
+    int best = 0;
+    for (int i = 0; i < n; ++i) {
+        if (v[i] != v[i]) return i;
+        if (v[i] > v[best]) best = i;
+    }
+    return best;
+}
+
 static int orc_best_edge(const orc_tree* t, const orc_node* node) {
     const orc_edge* e = t->edges + node->first;
     int64_t sum = 0;
     for (int i = 0; i < node->count; ++i) sum += e[i].N;
     double sq = orc_pow_half(sum);
-    int best = 0;
-    double best_v = 0.0;
+    double ucb[ORC_MAX_ACTIONS];
     for (int i = 0; i < node->count; ++i) {
         double q = e[i].N ? e[i].W / (double)e[i].N : 0.0;
         double u = t->g.c_puct * e[i].prior * sq / (double)(1 + e[i].N);
-        double ucb = q + u;
-        if (i == 0 || ucb > best_v) { best = i; best_v = ucb; }
+        ucb[i] = q + u;
     }
-    return best;
+    return orc_argmax_f64(ucb, node->count);
 }
 
 /* get_best_edge_with_noise (mcts.py:70-85): priors as the reference holds
@@ -496,20 +507,16 @@ static int orc_best_edge_noise(orc_tree* t, const orc_node* node) {
     int64_t sum = 0;
     for (int i = 0; i < node->count; ++i) sum += e[i].N;
     double sq = orc_pow_half(sum);
-    int best = 0;
-    double best_v = 0.0;
+    double ucb[ORC_MAX_ACTIONS];
     for (int i = 0; i < node->count; ++i) {
         double kept = node->prior64 ? (1 - orc_noise_ratio) * e[i].prior
                                     : (double)((float)(1 - orc_noise_ratio) * (float)e[i].prior);
         double noisy = kept + orc_noise_ratio * d[i];
         double q = e[i].N ? e[i].W / (double)e[i].N : 0.0;
         double u = t->g.c_puct * noisy * sq / (double)(1 + e[i].N);
-        double ucb = q + u;
-        if (i == 0) { best = 0; best_v = ucb; continue; }
-        if (best_v != best_v) continue;                       /* a NaN already holds the max */
-        if (ucb != ucb || ucb > best_v) { best = i; best_v = ucb; }
+        ucb[i] = q + u;
     }
-    return best;
+    return orc_argmax_f64(ucb, node->count);
 }
 
 /* evaluate_and_expand: returns the leaf's value (side to move at the leaf) */

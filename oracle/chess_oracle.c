@@ -709,6 +709,7 @@ typedef struct {
 void orc_mt_seed(orc_mt* s, uint32_t seed);
 double orc_mt_uniform(orc_mt* s);
 int orc_normalize_f32(const float* p, int n, double* out);
+int orc_argmax_f64(const double* v, int n);
 void orc_normalize_f64(const double* p, int n, double* out);
 double orc_pow_half(int64_t n);
 
@@ -805,18 +806,20 @@ static int ct_best_edge(const ctree* t, const cnode* node) {
     int64_t sum = 0;
     for (int i = 0; i < node->count; ++i) sum += e[i].N;
     double sq = orc_pow_half(sum);
-    int best = 0;
-    double best_v = 0.0;
+    double ucb[256];
     for (int i = 0; i < node->count; ++i) {
         double q = e[i].N ? e[i].W / (double)e[i].N : 0.0;
         double u = t->c_puct * e[i].prior * sq / (double)(1 + e[i].N);
-        double ucb = q + u;
-        if (i == 0 || ucb > best_v) {
-            best = i;
-            best_v = ucb;
-        }
+        ucb[i] = q + u;
     }
+#ifdef ORC_CHESS_KEPT_RULE /* scratch builds of tests/test_select_order_cpu.py only: first element, then strict > */
+    int best = 0;
+    for (int i = 1; i < node->count; ++i)
+        if (ucb[i] > ucb[best]) best = i;
     return best;
+#else
+    return orc_argmax_f64(ucb, node->count); /* np.argmax (mcts.py:64-68) */
+#endif
 }
 
 static double ct_expand(ctree* t, int node_id) {

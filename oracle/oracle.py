@@ -47,6 +47,8 @@ def lib():
         L.orc_pow_half.argtypes = [ctypes.c_int64]
         L.orc_seed_uniform.restype = ctypes.c_double
         L.orc_seed_uniform.argtypes = [ctypes.c_uint32, ctypes.c_int]
+        L.orc_argmax_f64.restype = ctypes.c_int
+        L.orc_argmax_f64.argtypes = [P, ctypes.c_int]
         L.orc_choice.restype = ctypes.c_int
         L.orc_choice.argtypes = [P, ctypes.c_int, ctypes.c_double]
         L.orc_normalize_f32.restype = ctypes.c_int
@@ -91,6 +93,12 @@ def pow_half(n):
 
 def seed_uniform(seed, k):
     return lib().orc_seed_uniform(int(seed), int(k))
+
+
+def argmax_f64(v):
+    """the oracles' best-edge choice: np.argmax over a list of Python floats"""
+    v = np.ascontiguousarray(v, np.float64)
+    return lib().orc_argmax_f64(_ptr(v), len(v))
 
 
 def choice(p, u):
