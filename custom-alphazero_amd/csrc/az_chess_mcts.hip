@@ -36,7 +36,7 @@
 #include "../../include/az_chess.h"
 #include "az_chess.h"
 #include "az_dirichlet_wave.h"
-#include "az_host.h"
+#include "az_session.h"
 #include "az_nn.h"
 #include "az_tree.h"
 
@@ -1091,25 +1091,18 @@ using namespace azc;
 // A lane = a contiguous slot group searched on its own HIP stream: its
 // simulations' tree kernels and network launches overlap the other lanes'
 // (a 256-game step is latency-bound: one launch fills half the CUs).
-struct CLane {
-  int first = 0;
-  hipStream_t stream = nullptr;
+struct CLane : az::EvalLane {  // counts: [2] pairs of eval queue and duplicate counters
   CCfg g{};
   CTree t{};
-  float* x = nullptr;
-  float* act[3] = {nullptr, nullptr, nullptr};
-  float* probs = nullptr;
-  float* values = nullptr;
-  az::ConvTimer timer;
-  int32_t* counts = nullptr;  // [2] the eval queue counters, alternating by simulation
   int par = 0;
   bool pending_expand = false;  // the last simulation's expand not launched yet
   ChessCache cache{};  // the engine's (flush_expand has no engine pointer)
 };
 
-struct az_chess_engine {
-  int device = 0;
-  hipStream_t stream = nullptr;
+// The session's streams: `stream`, one of its own per lane, and the drain's own
+// pack stream (asynchronous steps + drain, ABI 10, as the Connect-N engine: the
+// drain copies the games of the clock's newest complete snapshot on pack_stream).
+struct az_chess_engine : az::Session {
   az_chess_config cfg{};
   CCfg g{};
   CTree t{};
@@ -1118,18 +1111,6 @@ struct az_chess_engine {
   ChessCache cache{};  // the transposition cache (az_chess_config.cache_log2; enabled = 0 when off)
   az::NetDev net{};
   az::ConvTimer timer;
-  hipEvent_t timer_ref = nullptr;
-  float* x = nullptr;
-  float* act[3] = {nullptr, nullptr, nullptr};
-  float* probs = nullptr;
-  float* values = nullptr;
-  az::DeviceAllocs mem;
-  az::DeviceAllocs samples;  // the self-play sample buffers, re-made at every az_chess_selfplay_begin
-  int64_t sp_n = 0;
-  // asynchronous steps + drain (ABI 10), as the Connect-N engine: the drain
-  // copies the games of the clock's newest complete snapshot on pack_stream
-  az::MoveClock clock;
-  hipStream_t pack_stream = nullptr;
   // tree API staging (allocated on first use)
   double* tree_u = nullptr;
   int32_t *tree_move = nullptr, *tree_status = nullptr, *tree_pol_n = nullptr, *tree_slots = nullptr;
@@ -1139,17 +1120,6 @@ struct az_chess_engine {
   double* noise_buf = nullptr;  // az_chess_tree_search_noise: the caller's root-noise rows
   size_t noise_cap = 0;
   int32_t* noise_cur = nullptr;
-  // AZ_EVAL_HOST: the callback and its pinned staging buffers (slots leaves)
-  az_eval_fn host_fn = nullptr;
-  void* host_user = nullptr;
-  float* host_x = nullptr;
-  float* host_p = nullptr;
-  float* host_v = nullptr;
-  int32_t* host_n = nullptr;
-  // a host evaluator failed mid-simulation (AZ_E_CALLBACK): the leaves it
-  // selected were never expanded, so the trees are one simulation short;
-  // searching refuses until az_chess_selfplay_begin or az_chess_tree_reset
-  bool broken = false;
 };
 
 namespace {
@@ -1162,40 +1132,17 @@ int check_errors(az_chess_engine* e) {
 // (the reference's self.model(np.expand_dims(board.full_state, 0)),
 // mcts.py:130-137, here over every leaf of the lane's simulation at once), its
 // outputs back to the lane's evaluator slices.  Synchronous on the lane's
-// stream: after the first wait the select launch is complete, so the count
-// and the planes are final and the fused expand has read the previous
-// simulation's probs / values; after the last one the staging buffers are
-// free for the next lane.
+// stream: after HostEval::run's first wait the select launch is complete, so
+// the fused expand has read the previous simulation's probs / values.
 int host_evaluate(az_chess_engine* e, CLane& L) {
-  hipStream_t s = L.stream;
-  const int S = L.g.slots;
-  constexpr size_t kRow = (size_t)64 * AZ_CHESS_PLANES;
-  encode_host_kernel<<<std::min(S, 2048), 256, 0, s>>>(L.g, L.t, L.x);
+  encode_host_kernel<<<std::min(L.n, 2048), 256, 0, L.stream>>>(L.g, L.t, L.x);
   AZ_HIP(hipGetLastError());
-  AZ_HIP(hipMemcpyAsync(e->host_n, L.t.eval_count, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  AZ_HIP(hipStreamSynchronize(s));
-  const int n = *e->host_n;
-  if (n <= 0) return 0;
-  if (n > S) return az::fail_abi(AZ_E_DEVICE, "host evaluator: leaf count past the lane's slots");
-  AZ_HIP(hipMemcpyAsync(e->host_x, L.x, (size_t)n * kRow * sizeof(float), hipMemcpyDeviceToHost, s));
-  AZ_HIP(hipStreamSynchronize(s));
-  if (e->host_fn(e->host_user, e->host_x, n, e->host_p, e->host_v) != 0)
-    return az::fail_abi(AZ_E_CALLBACK, "the host evaluator returned an error");
-  AZ_HIP(hipMemcpyAsync(L.probs, e->host_p, (size_t)n * AZ_CHESS_ACTIONS * sizeof(float), hipMemcpyHostToDevice, s));
-  AZ_HIP(hipMemcpyAsync(L.values, e->host_v, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s));
-  AZ_HIP(hipStreamSynchronize(s));
-  return 0;
+  return e->host.run(L.stream, L.x, L.t.eval_count, L.n, (size_t)64 * AZ_CHESS_PLANES, AZ_CHESS_ACTIONS, L.probs,
+                     L.values);
 }
 
 int ready_to_search(az_chess_engine* e) {
-  if (e->broken)
-    return az::fail_abi(AZ_E_STATE, "a host evaluator error interrupted a simulation: the trees are incomplete "
-                                    "until az_chess_selfplay_begin or az_chess_tree_reset");
-  if (e->cfg.evaluator == AZ_EVAL_NETWORK && !e->net.ready)
-    return az::fail_abi(AZ_E_STATE, "network evaluator selected but az_chess_engine_set_weights was not called");
-  if (e->cfg.evaluator == AZ_EVAL_HOST && !e->host_fn)
-    return az::fail_abi(AZ_E_STATE, "host evaluator selected but az_chess_engine_set_evaluator was not called");
-  return 0;
+  return e->ready_to_search(e->cfg.evaluator, e->net.ready, "az_chess_");
 }
 
 int simulate(az_chess_engine* e, CLane& L) {
@@ -1262,16 +1209,9 @@ int flush_expand(CLane& L) {
   return 0;
 }
 
-int sync_lanes(az_chess_engine* e) {
-  for (CLane* L : e->lanes) AZ_HIP(hipStreamSynchronize(L->stream));
-  AZ_HIP(hipStreamSynchronize(e->stream));
-  return 0;
-}
-
 // lane view: per-slot arrays offset to the lane's first slot, its own eval
 // queue counter and evaluator buffer slices
 int make_lane(az_chess_engine* e, CLane* L, int first, int n) {
-  L->first = first;
   L->g = e->g;
   L->g.slots = n;
   CTree t = e->t;
@@ -1316,13 +1256,8 @@ int make_lane(az_chess_engine* e, CLane* L, int first, int n) {
   t.epoch = 0;
   L->cache = e->cache;
   L->t = t;
-  if (e->x) L->x = e->x + f * 64 * (e->g.evaluator == AZ_EVAL_HOST ? AZ_CHESS_PLANES : 128);
-  for (int i = 0; i < 3; ++i) L->act[i] = e->act[i] ? e->act[i] + f * 64 * 128 : nullptr;
-  L->probs = e->probs + f * AZ_CHESS_ACTIONS;
-  L->values = e->values + f;
-  if (hipStreamCreateWithFlags(&L->stream, hipStreamNonBlocking) != hipSuccess)
-    return az::fail_abi(AZ_E_HIP, "hipStreamCreate failed");
-  return 0;
+  e->slice(*L, first, n, 64 * (e->g.evaluator == AZ_EVAL_HOST ? AZ_CHESS_PLANES : 128), 64 * 128, AZ_CHESS_ACTIONS);
+  return e->new_lane_stream(&L->stream);
 }
 
 }  // namespace
@@ -1374,11 +1309,10 @@ int az_chess_engine_create(int device, const az_chess_config* cfg, az_chess_engi
     az_chess_engine_destroy(e);
     return rc;
   };
-  if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess)
-    return cleanup(az::fail_abi(AZ_E_HIP, "hipStreamCreate failed"));
+  int rc;
+  if ((rc = e->new_stream(&e->stream))) return cleanup(rc);
   const size_t S = (size_t)g.slots;
   CTree& t = e->t;
-  int rc;
   if ((rc = e->mem.alloc(&t.edges, S * 2 * (size_t)g.half_cap, false)) || (rc = e->mem.alloc(&t.root, S, false)) ||
       (rc = e->mem.alloc(&t.root_first, S, false)) || (rc = e->mem.alloc(&t.root_n, S, false)) || (rc = e->mem.alloc(&t.root_f64, S, false)) ||
       (rc = e->mem.alloc(&t.half, S, false)) ||
@@ -1419,12 +1353,9 @@ int az_chess_engine_create(int device, const az_chess_config* cfg, az_chess_engi
   }
   if (c.evaluator == AZ_EVAL_HOST) {
     // the leaves' dense rows [S][64][118] and their pinned host copy, the callback's outputs
-    if ((rc = e->mem.alloc(&e->x, S * 64 * AZ_CHESS_PLANES, false))) return cleanup(rc);
-    if (hipHostMalloc(&e->host_x, S * 64 * AZ_CHESS_PLANES * sizeof(float), hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc(&e->host_p, S * AZ_CHESS_ACTIONS * sizeof(float), hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc(&e->host_v, S * sizeof(float), hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc(&e->host_n, sizeof(int32_t), hipHostMallocDefault) != hipSuccess)
-      return cleanup(az::fail_abi(AZ_E_HIP, "host evaluator staging allocation failed"));
+    if ((rc = e->mem.alloc(&e->x, S * 64 * AZ_CHESS_PLANES, false)) ||
+        (rc = e->host.create(S, (size_t)64 * AZ_CHESS_PLANES, AZ_CHESS_ACTIONS)))
+      return cleanup(rc);
   }
   t.mt_stride = g.slots;
   // the transposition cache (mcts.py:122-143 on chess boards)
@@ -1462,32 +1393,15 @@ int az_chess_engine_create(int device, const az_chess_config* cfg, az_chess_engi
   if ((rc = e->clock.create(e->mem, nl, "drain snapshot allocation failed"))) return cleanup(rc);
   if (hipStreamCreateWithFlags(&e->pack_stream, hipStreamNonBlocking) != hipSuccess)
     return cleanup(az::fail_abi(AZ_E_HIP, "drain snapshot allocation failed"));
+  e->own_pack_stream = true;
   *out = e;
   return 0;
 }
 
 int az_chess_engine_destroy(az_chess_engine* e) {
   if (!e) return 0;
-  (void)hipSetDevice(e->device);
-  if (e->stream) (void)hipStreamSynchronize(e->stream);
-  for (CLane* L : e->lanes) {
-    if (L->stream) {
-      (void)hipStreamSynchronize(L->stream);
-      (void)hipStreamDestroy(L->stream);
-    }
-    delete L;
-  }
-  if (e->pack_stream) {
-    (void)hipStreamSynchronize(e->pack_stream);
-    (void)hipStreamDestroy(e->pack_stream);
-  }
-  e->clock.destroy();
-  e->samples.free_all();
-  e->mem.free_all();
-  if (e->timer_ref) (void)hipEventDestroy(e->timer_ref);
-  for (void* q : {(void*)e->host_x, (void*)e->host_p, (void*)e->host_v, (void*)e->host_n})
-    if (q) (void)hipHostFree(q);
-  if (e->stream) (void)hipStreamDestroy(e->stream);
+  e->destroy();
+  for (CLane* L : e->lanes) delete L;
   delete e;
   return 0;
 }
@@ -1496,11 +1410,9 @@ int az_chess_engine_set_evaluator(az_chess_engine* e, az_eval_fn fn, void* user)
   if (!e || !fn) return az::fail_abi(AZ_E_INVALID, "null argument");
   if (e->cfg.evaluator != AZ_EVAL_HOST)
     return az::fail_abi(AZ_E_STATE, "the engine was not created with AZ_EVAL_HOST");
-  AZ_HIP(hipSetDevice(e->device));
-  int rc;
-  if ((rc = sync_lanes(e))) return rc;
-  e->host_fn = fn;
-  e->host_user = user;
+  AZ_TRY(e->enter());
+  e->host.fn = fn;
+  e->host.user = user;
   if (e->cache.state) {  // cached outputs belong to the previous evaluator
     AZ_TRY(az::cache_clear(e->cache, nullptr));
     AZ_HIP(hipStreamSynchronize(nullptr));
@@ -1511,9 +1423,7 @@ int az_chess_engine_set_evaluator(az_chess_engine* e, az_eval_fn fn, void* user)
 int az_chess_engine_set_weights(az_chess_engine* e, const az_tensor* tensors, int n) {
   if (!e || (!tensors && n)) return az::fail_abi(AZ_E_INVALID, "null argument");
   if (e->cfg.evaluator != AZ_EVAL_NETWORK) return az::fail_abi(AZ_E_STATE, "engine has no network evaluator");
-  AZ_HIP(hipSetDevice(e->device));
-  int rc;
-  if ((rc = sync_lanes(e))) return rc;
+  AZ_TRY(e->enter());
   if (e->cache.state) {  // a new model empties plays_inferences (self_play.py:145-146)
     AZ_TRY(az::cache_clear(e->cache, nullptr));
     AZ_HIP(hipStreamSynchronize(nullptr));
@@ -1526,7 +1436,7 @@ int az_chess_forward(az_chess_engine* e, const float* x, int n, float* probs, fl
   if (!e || n < 0 || (n && (!x || !probs || !values))) return az::fail_abi(AZ_E_INVALID, "bad arguments");
   if (e->cfg.evaluator != AZ_EVAL_NETWORK) return az::fail_abi(AZ_E_STATE, "engine has no network evaluator");
   if (!e->net.ready) return az::fail_abi(AZ_E_STATE, "az_chess_engine_set_weights was not called");
-  AZ_HIP(hipSetDevice(e->device));
+  AZ_TRY(e->enter());  // (the lanes of an asynchronous step use slices of x, act, probs and values)
   const int chunk = e->g.slots;
   for (int off = 0; off < n; off += chunk) {
     const int m = std::min(chunk, n - off);
@@ -1551,11 +1461,10 @@ int az_chess_selfplay_begin(az_chess_engine* e, int64_t first_game, int64_t n_ga
   if (!e || n_games < 0 || first_game < 0) return az::fail_abi(AZ_E_INVALID, "bad arguments");
   if (e->cfg.evaluator == AZ_EVAL_NETWORK && !e->net.ready)
     return az::fail_abi(AZ_E_STATE, "network evaluator selected but az_chess_engine_set_weights was not called");
-  AZ_HIP(hipSetDevice(e->device));
   e->broken = false;  // every slot starts a fresh game
   for (CLane* L : e->lanes) L->pending_expand = false;  // (a search an error interrupted)
+  AZ_TRY(e->enter());
   int rc;
-  if ((rc = sync_lanes(e))) return rc;
   e->samples.free_all();
   CSamples& smp = e->smp;
   smp = CSamples{};
@@ -1573,23 +1482,16 @@ int az_chess_selfplay_begin(az_chess_engine* e, int64_t first_game, int64_t n_ga
       (rc = sb.alloc_zeroed_async(&smp.expansions, G, s)) || (rc = sb.alloc_zeroed_async(&smp.done_ids, G, s)) ||
       (rc = sb.alloc_zeroed_async(&smp.done_count, 1, s)))
     return rc;
-  e->clock.begin_batch();
-  unsigned long long st[az::kStatCount] = {0};
-  const int64_t first_wave = std::min<int64_t>(n_games, e->g.slots);
-  st[az::kStatNextGame] = (unsigned long long)(first_game + first_wave);
-  AZ_HIP(hipMemcpyAsync(e->t.stats, st, sizeof(st), hipMemcpyHostToDevice, e->stream));
-  slot_init_kernel<<<(e->g.slots + 255) / 256, 256, 0, e->stream>>>(e->g, e->t, smp, first_wave);
-  AZ_HIP(hipGetLastError());
-  AZ_HIP(hipStreamSynchronize(e->stream));
-  e->sp_n = n_games;
-  return 0;
+  return e->begin_batch(e->t.stats, e->g.slots, first_game, n_games, [&](int64_t first_wave) {
+    slot_init_kernel<<<(e->g.slots + 255) / 256, 256, 0, e->stream>>>(e->g, e->t, smp, first_wave);
+    return 0;
+  });
 }
 
 int az_chess_stats(az_chess_engine* e, az_stats* st) {
   if (!e || !st) return az::fail_abi(AZ_E_INVALID, "null argument");
-  AZ_HIP(hipSetDevice(e->device));
+  AZ_TRY(e->enter());
   int rc;
-  if ((rc = sync_lanes(e))) return rc;
   unsigned long long h[az::kStatCount];
   if ((rc = az::read_common_stats(st, h, e->t.stats, e->t.game_id, e->g.slots, e->cache)))
     return rc;
@@ -1606,25 +1508,11 @@ int az_chess_selfplay_step(az_chess_engine* e, int n_moves, az_stats* st) {
   if (!e->smp.done_count) return az::fail_abi(AZ_E_STATE, "az_chess_selfplay_begin was not called");
   int rc;
   if ((rc = ready_to_search(e))) return rc;
-  AZ_HIP(hipSetDevice(e->device));
-  for (int mv = 0; mv < n_moves; ++mv) {
-    const int64_t m = e->clock.issued++;
-    // lanes interleaved per simulation so every stream always has work queued
-    for (int s = 0; s < e->g.sims; ++s)
-      for (CLane* L : e->lanes)
-        if ((rc = simulate(e, *L))) return rc;
-    for (CLane* L : e->lanes)
-      if ((rc = flush_expand(*L))) return rc;
-    for (size_t l = 0; l < e->lanes.size(); ++l) {
-      CLane* L = e->lanes[l];
-      if ((rc = e->clock.before_play(m, l, L->stream))) return rc;
-      play_kernel<<<L->g.slots, 64, 0, L->stream>>>(L->g, L->t, e->smp, CPlayOut{});
-      if ((rc = e->clock.after_play(m, l, L->stream, e->smp.done_count))) return rc;
-    }
-    AZ_HIP(hipGetLastError());
-  }
-  if (!st) return 0;  // asynchronous (ABI 10): the moves run on while the caller drains earlier ones
-  if ((rc = sync_lanes(e))) return rc;
+  rc = e->step_moves(
+      n_moves, e->g.sims, e->lanes, e->smp.done_count, [&](CLane& L) { return simulate(e, L); }, flush_expand,
+      [&](CLane& L) { play_kernel<<<L.n, 64, 0, L.stream>>>(L.g, L.t, e->smp, CPlayOut{}); });
+  if (rc || !st) return rc;  // st = NULL, asynchronous (ABI 10): the moves run on while the caller drains earlier ones
+  if ((rc = e->sync_all())) return rc;
   if ((rc = check_errors(e))) return rc;
   return az_chess_stats(e, st);
 }
@@ -1679,24 +1567,16 @@ int az_chess_selfplay_drain(az_chess_engine* e, int64_t max_games, int64_t* n_ou
 
 int az_chess_selfplay_run(az_chess_engine* e, int64_t first_game, int64_t n_games, uint32_t base_seed,
                           az_stats* st) {
-  int rc;
-  if ((rc = az_chess_selfplay_begin(e, first_game, n_games, base_seed))) return rc;
-  az_stats tmp;
-  for (;;) {
-    if ((rc = az_chess_selfplay_step(e, 1, &tmp))) return rc;
-    if (tmp.active_slots == 0) break;
-  }
-  if (st) *st = tmp;
-  return 0;
+  return az::run_to_end(
+      st, [&] { return az_chess_selfplay_begin(e, first_game, n_games, base_seed); },
+      [&](az_stats* now) { return az_chess_selfplay_step(e, 1, now); });
 }
 
 int az_chess_selfplay_results(az_chess_engine* e, int32_t* lengths, int32_t* results, int32_t* terminations,
                               int32_t* expansions, az_chess_pos* positions, uint16_t* moves, int32_t* policy_n,
                               int16_t* policy_actions, double* policy_probs) {
   if (!e) return az::fail_abi(AZ_E_INVALID, "null engine");
-  AZ_HIP(hipSetDevice(e->device));
-  int rc;
-  if ((rc = sync_lanes(e))) return rc;
+  AZ_TRY(e->enter());
   const size_t G = (size_t)e->sp_n, P = (size_t)e->smp.plies, M = AZ_CHESS_MAX_MOVES;
   if (G == 0) return 0;
   const CSamples& s = e->smp;
@@ -1745,10 +1625,9 @@ int az_chess_tree_reset(az_chess_engine* e, int n, const int32_t* slots, const a
   if (!e || (n && !roots)) return az::fail_abi(AZ_E_INVALID, "null argument");
   if (e->cfg.evaluator == AZ_EVAL_NETWORK && !e->net.ready)
     return az::fail_abi(AZ_E_STATE, "network evaluator selected but az_chess_engine_set_weights was not called");
-  AZ_HIP(hipSetDevice(e->device));
+  AZ_TRY(e->enter());
   for (CLane* L : e->lanes) L->pending_expand = false;  // (a search an error interrupted)
-  int rc;
-  if ((rc = sync_lanes(e)) || (rc = tree_slot_list(e, n, slots))) return rc;
+  AZ_TRY(tree_slot_list(e, n, slots));
   if (!n) return 0;
   // a root must be a position the device rules accept (legal move list fits)
   std::vector<az_chess_pos> r(roots, roots + n);
@@ -1765,9 +1644,8 @@ int az_chess_tree_reset(az_chess_engine* e, int n, const int32_t* slots, const a
 
 int az_chess_tree_release(az_chess_engine* e, int n, const int32_t* slots) {
   if (!e) return az::fail_abi(AZ_E_INVALID, "null engine");
-  AZ_HIP(hipSetDevice(e->device));
-  int rc;
-  if ((rc = sync_lanes(e)) || (rc = tree_slot_list(e, n, slots))) return rc;
+  AZ_TRY(e->enter());
+  AZ_TRY(tree_slot_list(e, n, slots));
   if (!n) return 0;
   tree_release_kernel<<<(n + 63) / 64, 64, 0, e->stream>>>(e->t, n, e->tree_slots);
   AZ_HIP(hipGetLastError());
@@ -1782,13 +1660,13 @@ int az_chess_tree_search(az_chess_engine* e, int n_sims) {
                                       "az_chess_tree_search_noise (the caller's np.random.dirichlet draws)");
   int rc;
   if ((rc = ready_to_search(e))) return rc;
-  AZ_HIP(hipSetDevice(e->device));
+  AZ_TRY(e->enter());
   for (int s = 0; s < n_sims; ++s)
     for (CLane* L : e->lanes)
       if ((rc = simulate(e, *L))) return rc;
   for (CLane* L : e->lanes)
     if ((rc = flush_expand(*L))) return rc;
-  if ((rc = sync_lanes(e))) return rc;
+  if ((rc = e->sync_all())) return rc;
   return check_errors(e);
 }
 
@@ -1798,8 +1676,7 @@ int az_chess_tree_search_noise(az_chess_engine* e, int n_sims, const double* noi
     return az::fail_abi(AZ_E_INVALID, "az_chess_tree_search_noise needs an engine created with dirichlet_noise = 1");
   int rc;
   if ((rc = ready_to_search(e))) return rc;
-  AZ_HIP(hipSetDevice(e->device));
-  if ((rc = sync_lanes(e))) return rc;
+  AZ_TRY(e->enter());
   const size_t S = (size_t)e->g.slots, M = AZ_CHESS_MAX_MOVES, n = S * (size_t)std::max(rows, 1) * M;
   if (n > e->noise_cap) {  // grown on demand, kept for the next searches
     double* buf = nullptr;
@@ -1828,7 +1705,7 @@ int az_chess_tree_search_noise(az_chess_engine* e, int n_sims, const double* noi
   if (rc) return rc;
   for (CLane* L : e->lanes)
     if ((rc = flush_expand(*L))) return rc;
-  if ((rc = sync_lanes(e))) return rc;
+  if ((rc = e->sync_all())) return rc;
   return check_errors(e);
 }
 
@@ -1836,9 +1713,9 @@ int az_chess_tree_play(az_chess_engine* e, const double* uniforms, int greedy, i
                        int32_t* status, int32_t* policy_n, int16_t* policy_actions, double* policy_probs) {
   if (!e || (!deterministic && !uniforms)) return az::fail_abi(AZ_E_INVALID, "bad arguments");
   if (e->broken) return ready_to_search(e);
-  AZ_HIP(hipSetDevice(e->device));
+  AZ_TRY(e->enter());
   int rc;
-  if ((rc = sync_lanes(e)) || (rc = tree_buffers(e))) return rc;
+  if ((rc = tree_buffers(e))) return rc;
   const size_t S = (size_t)e->g.slots, M = AZ_CHESS_MAX_MOVES;
   if (!deterministic) AZ_HIP(hipMemcpyAsync(e->tree_u, uniforms, S * sizeof(double), hipMemcpyHostToDevice, e->stream));
   AZ_HIP(hipMemsetAsync(e->tree_move, 0xff, S * sizeof(int32_t), e->stream));
@@ -1859,7 +1736,7 @@ int az_chess_tree_play(az_chess_engine* e, const double* uniforms, int greedy, i
     play_kernel<<<L->g.slots, 64, 0, L->stream>>>(L->g, L->t, CSamples{}, po);
   }
   AZ_HIP(hipGetLastError());
-  if ((rc = sync_lanes(e)) || (rc = check_errors(e))) return rc;
+  if ((rc = e->sync_all()) || (rc = check_errors(e))) return rc;
   if (moves) AZ_HIP(hipMemcpy(moves, e->tree_move, S * sizeof(int32_t), hipMemcpyDeviceToHost));
   if (status) AZ_HIP(hipMemcpy(status, e->tree_status, S * sizeof(int32_t), hipMemcpyDeviceToHost));
   if (policy_n) AZ_HIP(hipMemcpy(policy_n, e->tree_pol_n, S * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -1870,9 +1747,7 @@ int az_chess_tree_play(az_chess_engine* e, const double* uniforms, int greedy, i
 
 int az_chess_tree_info(az_chess_engine* e, int slot, int64_t* info, float* root_value) {
   if (!e || !info || slot < 0 || slot >= e->g.slots) return az::fail_abi(AZ_E_INVALID, "bad arguments");
-  AZ_HIP(hipSetDevice(e->device));
-  int rc;
-  if ((rc = sync_lanes(e))) return rc;
+  AZ_TRY(e->enter());
   int32_t top, first, cnt, ply;
   int64_t gid;
   AZ_HIP(hipMemcpy(&top, e->t.top + slot, 4, hipMemcpyDeviceToHost));
@@ -1892,9 +1767,7 @@ int az_chess_tree_info(az_chess_engine* e, int slot, int64_t* info, float* root_
 int az_chess_tree_export(az_chess_engine* e, int slot, double* prior, double* w, int32_t* n, int32_t* child,
                          int32_t* child_n, int32_t* moves, float* child_value) {
   if (!e || slot < 0 || slot >= e->g.slots) return az::fail_abi(AZ_E_INVALID, "bad arguments");
-  AZ_HIP(hipSetDevice(e->device));
-  int rc;
-  if ((rc = sync_lanes(e))) return rc;
+  AZ_TRY(e->enter());
   int32_t top, half;
   AZ_HIP(hipMemcpy(&top, e->t.top + slot, 4, hipMemcpyDeviceToHost));
   AZ_HIP(hipMemcpy(&half, e->t.half + slot, 4, hipMemcpyDeviceToHost));
@@ -1916,9 +1789,7 @@ int az_chess_tree_export(az_chess_engine* e, int slot, double* prior, double* w,
 
 int az_chess_timer_enable(az_chess_engine* e, int on) {
   if (!e) return az::fail_abi(AZ_E_INVALID, "null engine");
-  AZ_HIP(hipSetDevice(e->device));
-  int rc;
-  if ((rc = sync_lanes(e))) return rc;
+  AZ_TRY(e->enter());
   std::vector<az::ConvTimer*> timers = {&e->timer};
   for (CLane* L : e->lanes) timers.push_back(&L->timer);
   return az::arm_timers(&e->timer_ref, e->stream, timers, on != 0, 1);

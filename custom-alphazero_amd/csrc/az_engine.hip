@@ -12,7 +12,7 @@
 #include <vector>
 
 #include "../../include/az.h"
-#include "az_host.h"
+#include "az_session.h"
 #include "az_mt.h"
 #include "az_nn.h"
 #include "az_tree.h"
@@ -42,24 +42,19 @@ const int g_hw_queues_at_load = read_hw_queues();
 // other's launch tails and small latency-bound kernels; results do not
 // depend on the lane count (each game's search only reads its own tree and
 // the evaluator is deterministic per board).
-struct Lane {
-  int first = 0, n = 0;
-  int32_t* counts = nullptr;  // [2][4][kCountStride] eval/miss/nn/dup counts by simulation parity
-  hipStream_t stream = nullptr;
+struct Lane : az::EvalLane {  // counts: [2][4][kCountStride], a block of eval/miss/nn counts per simulation parity
   az::GameCfg g{};
   az::TreeDev t{};
-  float* x = nullptr;
-  float* act[3] = {nullptr, nullptr, nullptr};
-  float* probs = nullptr;
-  float* values = nullptr;
-  az::ConvTimer timer;
   az::ConvTimer tree_timer;  // select and expand launches (bench.py roofline_tree)
   int64_t pool_cap = 0;        // compacted self-play: edges per pool half (TreeDev::pool_cap)
 };
 
-struct az_engine {
-  int device = 0;
-  hipStream_t stream = nullptr;
+// The session's streams: `stream`, the lanes' own when there is more than one
+// lane, and the drain's pack stream.  The pack has no stream of its own with
+// two or more lanes: HIP maps streams onto 4 hardware queues per process
+// (GPU_MAX_HW_QUEUES), and a snapshot or pack stream sharing a lane's queue
+// runs behind that lane's queued moves -- it uses `stream`, idle while moves run.
+struct az_engine : az::Session {
   Lane whole;                // every slot on `stream` (tree API; self-play with one lane)
   std::vector<Lane*> lanes;  // self-play lanes (just &whole when there is one)
   az_config cfg{};
@@ -69,43 +64,15 @@ struct az_engine {
   az::CacheDev cache{};
   az::NetDev net{};
   az::ConvTimer timer;
-  float* x = nullptr;
-  float* act[3] = {nullptr, nullptr, nullptr};
-  float* probs = nullptr;
-  float* values = nullptr;
-  // AZ_EVAL_HOST: the callback and its pinned staging buffers (slots leaves)
-  az_eval_fn host_fn = nullptr;
-  void* host_user = nullptr;
-  float* host_x = nullptr;
-  float* host_p = nullptr;
-  float* host_v = nullptr;
-  int32_t* host_n = nullptr;
   double* uniforms = nullptr;
   double* noise_buf = nullptr;  // az_tree_search_noise: the caller's root-noise rows
   size_t noise_cap = 0;
   int32_t* dev_i32 = nullptr;  // scratch for az_tree_reset
   az::Board* dev_boards = nullptr;
-  az::DeviceAllocs mem;
-  az::DeviceAllocs samples;  // the self-play sample buffers, re-made at every az_selfplay_begin
-  std::vector<hipStream_t> lane_streams;
-  hipEvent_t timer_ref = nullptr;  // common origin of every ConvTimer's intervals
-  int64_t sp_first = 0, sp_n = 0;
   uint32_t leaf_epoch = 0;         // simulations enqueued, every lane's (TreeDev::leaf_epoch)
   uint8_t* drain_dev = nullptr;    // packed records (device) and their pinned host copy
   uint8_t* drain_host = nullptr;
-  // the drain packs up to a completed snapshot of the clock on pack_stream.
-  // No stream of its own: HIP maps streams onto 4 hardware queues per process
-  // (GPU_MAX_HW_QUEUES), and a snapshot or pack stream sharing a lane's queue
-  // runs behind that lane's queued moves -- with two lanes the pack uses
-  // `stream`, idle while moves run.
-  az::MoveClock clock;
-  hipStream_t pack_stream = nullptr;
-  bool own_pack_stream = false;
   size_t drain_cap = 0;            // records the two buffers hold
-  // a host evaluator failed mid-simulation (AZ_E_CALLBACK): the leaves it
-  // selected were never expanded, so the trees are one simulation short;
-  // searching refuses until az_selfplay_begin or az_tree_reset starts over
-  bool broken = false;
 };
 
 namespace {
@@ -143,26 +110,10 @@ void cells_from_board(const az::Board& b, int HW, int8_t* cells) {
 // here over every leaf of the simulation at once), its outputs back to the
 // lane's evaluator slices; synchronous on the lane's stream
 int host_evaluate(az_engine* e, Lane& L, const az::Board* rows, const int32_t* n_rows) {
-  hipStream_t s = L.stream;
-  const int HW = L.g.HW, A = L.g.A;
-  az::launch_encode(rows, n_rows, L.n, HW, L.x, s);
+  az::launch_encode(rows, n_rows, L.n, L.g.HW, L.x, L.stream);
   AZ_HIP(hipGetLastError());
-  AZ_HIP(hipMemcpyAsync(e->host_n, n_rows, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  AZ_HIP(hipStreamSynchronize(s));
-  const int n = *e->host_n;
-  if (n <= 0) return 0;
-  if (n > L.n) return fail(AZ_E_DEVICE, "host evaluator: leaf count past the lane's slots");
-  AZ_HIP(hipMemcpyAsync(e->host_x, L.x, (size_t)n * HW * 4 * sizeof(float), hipMemcpyDeviceToHost, s));
-  AZ_HIP(hipStreamSynchronize(s));
-  if (e->host_fn(e->host_user, e->host_x, n, e->host_p, e->host_v) != 0)
-    return fail(AZ_E_CALLBACK, "the host evaluator returned an error");
-  AZ_HIP(hipMemcpyAsync(L.probs, e->host_p, (size_t)n * A * sizeof(float), hipMemcpyHostToDevice, s));
-  AZ_HIP(hipMemcpyAsync(L.values, e->host_v, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s));
-  AZ_HIP(hipStreamSynchronize(s));  // the staging buffers are reused by the next lane
-  return 0;
+  return e->host.run(L.stream, L.x, n_rows, L.n, (size_t)L.g.HW * 4, L.g.A, L.probs, L.values);
 }
-
-int sync_all(az_engine* e);
 
 // one simulation for every active slot of a lane (MCTS.search body,
 // mcts.py:171-180), enqueued on the lane's stream
@@ -173,7 +124,7 @@ int simulate(az_engine* e, Lane& L) {
   // over the engine's lanes; when it wraps (2^32 simulations) the records are
   // cleared first, so none written 2^32 simulations ago can match
   if (++e->leaf_epoch == 0) {
-    if (int rc = sync_all(e)) return rc;
+    AZ_TRY(e->sync_all());
     AZ_HIP(hipMemset(e->t.leaf_src, 0, (size_t)e->g.slots * sizeof(uint64_t)));
     e->leaf_epoch = 1;
   }
@@ -209,22 +160,6 @@ int simulate(az_engine* e, Lane& L) {
   return 0;
 }
 
-int sync_all(az_engine* e) {
-  AZ_HIP(hipStreamSynchronize(e->stream));
-  for (hipStream_t s : e->lane_streams) AZ_HIP(hipStreamSynchronize(s));
-  if (e->own_pack_stream) AZ_HIP(hipStreamSynchronize(e->pack_stream));
-  return 0;
-}
-
-// Entry of an ABI call that reads or writes engine buffers: the device, then
-// every queued move finished (az_selfplay_step without stats returns while
-// the lanes' kernels run on non-blocking streams; their samples, trees and
-// evaluator slices must not be read or overwritten under them).
-int enter(az_engine* e) {
-  AZ_HIP(hipSetDevice(e->device));
-  return sync_all(e);
-}
-
 // the tree API never compacts (its views are the whole tree, like the
 // reference's object graph): an engine created with compact = 1 sizes each
 // arena half for one move, which a reused tree outgrows
@@ -234,25 +169,15 @@ int tree_api_ok(az_engine* e) {
   return 0;
 }
 
+// (the caller has entered: no move is running)
 int cache_clear(az_engine* e) {
   if (!e->cache.state) return 0;
-  int rc;
-  if ((rc = sync_all(e))) return rc;
-  if ((rc = az::cache_clear(e->cache, e->stream))) return rc;
+  AZ_TRY(az::cache_clear(e->cache, e->stream));
   AZ_HIP(hipStreamSynchronize(e->stream));
   return 0;
 }
 
-int ready_to_search(az_engine* e) {
-  if (e->broken)
-    return fail(AZ_E_STATE, "a host evaluator error interrupted a simulation: the trees are incomplete "
-                            "until az_selfplay_begin or az_tree_reset");
-  if (e->cfg.evaluator == AZ_EVAL_NETWORK && !e->net.ready)
-    return fail(AZ_E_STATE, "network evaluator selected but az_engine_set_weights was not called");
-  if (e->cfg.evaluator == AZ_EVAL_HOST && !e->host_fn)
-    return fail(AZ_E_STATE, "host evaluator selected but az_engine_set_evaluator was not called");
-  return 0;
-}
+int ready_to_search(az_engine* e) { return e->ready_to_search(e->cfg.evaluator, e->net.ready, "az_"); }
 
 // ------------------------------------------------------------ weight folding
 [[maybe_unused]] int fetch(const std::map<std::string, const az_tensor*>& m, const std::string& name,
@@ -342,8 +267,6 @@ int upload_new(az::DeviceAllocs& owned, T** dst, const std::vector<T>& src) {
 // one lane each gets its own eval-queue counters.
 int make_lane(az_engine* e, Lane* L, int first, int n, bool own_queue) {
   const az::GameCfg& g = e->g;
-  L->first = first;
-  L->n = n;
   L->g = g;
   L->g.slots = n;
   az::TreeDev t = e->t;
@@ -379,10 +302,7 @@ int make_lane(az_engine* e, Lane* L, int first, int n, bool own_queue) {
   }
   L->counts = t.eval_count;
   L->t = t;
-  L->x = e->x + f * g.HW * 4;
-  for (int i = 0; i < 3; ++i) L->act[i] = e->act[i] ? e->act[i] + f * g.HW * 128 : nullptr;
-  L->probs = e->probs + f * g.A;
-  L->values = e->values + f;
+  e->slice(*L, first, n, (size_t)g.HW * 4, (size_t)g.HW * 128, g.A);
   return 0;
 }
 
@@ -736,8 +656,7 @@ int az_engine_create(int device, const az_config* cfg, az_engine** out) {
     return rc;
   };
   int rc;
-  if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess)
-    return cleanup(fail(AZ_E_HIP, "hipStreamCreate failed"));
+  if ((rc = e->new_stream(&e->stream))) return cleanup(rc);
   if (c.lanes < 0) return cleanup(fail(AZ_E_INVALID, "lanes must be >= 0"));
   const size_t S = (size_t)g.slots;
   az::TreeDev& t = e->t;
@@ -790,13 +709,7 @@ int az_engine_create(int device, const az_config* cfg, az_engine** out) {
       (rc = e->mem.alloc(&e->dev_boards, S, false)))
     return cleanup(rc);
   if ((rc = e->mem.alloc(&e->x, S * g.HW * 4, false))) return cleanup(rc);
-  if (c.evaluator == AZ_EVAL_HOST) {
-    if (hipHostMalloc(&e->host_x, (size_t)S * g.HW * 4 * sizeof(float), hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc(&e->host_p, (size_t)S * A * sizeof(float), hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc(&e->host_v, (size_t)S * sizeof(float), hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc(&e->host_n, sizeof(int32_t), hipHostMallocDefault) != hipSuccess)
-      return cleanup(fail(AZ_E_HIP, "host evaluator staging allocation failed"));
-  }
+  if (c.evaluator == AZ_EVAL_HOST && (rc = e->host.create(S, (size_t)g.HW * 4, A))) return cleanup(rc);
   if (c.evaluator == AZ_EVAL_NETWORK) {
     const size_t act = S * g.HW * 128;
     for (int i = 0; i < 3; ++i)
@@ -836,12 +749,7 @@ int az_engine_create(int device, const az_config* cfg, az_engine** out) {
       Lane* L = new Lane();
       e->lanes.push_back(L);
       const int lo = (int)((int64_t)g.slots * l / nl), hi = (int)((int64_t)g.slots * (l + 1) / nl);
-      if ((rc = make_lane(e, L, lo, hi - lo, true))) return cleanup(rc);
-      hipStream_t st;
-      if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess)
-        return cleanup(fail(AZ_E_HIP, "hipStreamCreate failed"));
-      e->lane_streams.push_back(st);
-      L->stream = st;
+      if ((rc = make_lane(e, L, lo, hi - lo, true)) || (rc = e->new_lane_stream(&L->stream))) return cleanup(rc);
     }
   }
   e->net.lanes = (int)e->lanes.size();  // (the tower's dual-launch threshold, load_network)
@@ -852,12 +760,8 @@ int az_engine_create(int device, const az_config* cfg, az_engine** out) {
   // drain: one lane runs on `stream`, so the pack needs a stream of its own;
   // with more lanes `stream` is idle while moves run
   e->own_pack_stream = nl == 1;
-  if (e->own_pack_stream) {
-    if (hipStreamCreateWithFlags(&e->pack_stream, hipStreamNonBlocking) != hipSuccess)
-      return cleanup(fail(AZ_E_HIP, "hipStreamCreate failed"));
-  } else {
-    e->pack_stream = e->stream;
-  }
+  e->pack_stream = e->stream;
+  if (e->own_pack_stream && (rc = e->new_stream(&e->pack_stream))) return cleanup(rc);
   if ((rc = e->clock.create(e->mem, nl, "drain snapshot setup failed"))) return cleanup(rc);
   e->net.hidden = c.value_hidden;
   *out = e;
@@ -868,27 +772,11 @@ int az_engine_lanes(const az_engine* eng) { return eng ? (int)eng->lanes.size() 
 
 int az_engine_destroy(az_engine* eng) {
   if (!eng) return 0;
-  (void)hipSetDevice(eng->device);
-  if (eng->stream) (void)hipStreamSynchronize(eng->stream);
-  for (hipStream_t s : eng->lane_streams) {
-    (void)hipStreamSynchronize(s);
-    (void)hipStreamDestroy(s);
-  }
-  if (eng->own_pack_stream && eng->pack_stream) {
-    (void)hipStreamSynchronize(eng->pack_stream);
-    (void)hipStreamDestroy(eng->pack_stream);
-  }
-  eng->clock.destroy();
+  eng->destroy();
   for (Lane* L : eng->lanes)
     if (L != &eng->whole) delete L;
   if (eng->drain_dev) (void)hipFree(eng->drain_dev);
   if (eng->drain_host) (void)hipHostFree(eng->drain_host);
-  eng->samples.free_all();
-  eng->mem.free_all();
-  if (eng->timer_ref) (void)hipEventDestroy(eng->timer_ref);
-  for (void* q : {(void*)eng->host_x, (void*)eng->host_p, (void*)eng->host_v, (void*)eng->host_n})
-    if (q) (void)hipHostFree(q);
-  if (eng->stream) (void)hipStreamDestroy(eng->stream);
   delete eng;
   return 0;
 }
@@ -896,15 +784,15 @@ int az_engine_destroy(az_engine* eng) {
 int az_engine_set_evaluator(az_engine* e, az_eval_fn fn, void* user) {
   if (!e || !fn) return fail(AZ_E_INVALID, "null argument");
   if (e->cfg.evaluator != AZ_EVAL_HOST) return fail(AZ_E_STATE, "the engine was not created with AZ_EVAL_HOST");
-  if (int rc_ = enter(e)) return rc_;
-  e->host_fn = fn;
-  e->host_user = user;
+  AZ_TRY(e->enter());
+  e->host.fn = fn;
+  e->host.user = user;
   return cache_clear(e);  // cached outputs belong to the previous evaluator
 }
 
 int az_engine_set_weights(az_engine* e, const az_tensor* tensors, int n) {
   if (!e || (!tensors && n)) return fail(AZ_E_INVALID, "null argument");
-  if (int rc_ = enter(e)) return rc_;
+  AZ_TRY(e->enter());
   int rc;
   if ((rc = az::load_network(e->net, tensors, n, 4, e->g.HW, e->g.A, e->cfg.bn_epsilon, e->mem)))
     return rc;
@@ -913,7 +801,7 @@ int az_engine_set_weights(az_engine* e, const az_tensor* tensors, int n) {
 
 int az_encode(az_engine* e, const int8_t* boards, int n, float* state, uint8_t* mask) {
   if (!e || n < 0 || (n && !boards)) return fail(AZ_E_INVALID, "bad arguments");
-  if (int rc_ = enter(e)) return rc_;
+  AZ_TRY(e->enter());
   const int HW = e->g.HW, A = e->g.A;
   const int chunk = e->g.slots;
   std::vector<az::Board> hb(std::min(n, chunk));
@@ -939,7 +827,7 @@ int az_encode(az_engine* e, const int8_t* boards, int n, float* state, uint8_t* 
 int az_forward(az_engine* e, const float* x, int n, float* probs, float* values) {
   if (!e || n < 0 || (n && (!x || !probs || !values))) return fail(AZ_E_INVALID, "bad arguments");
   if (!e->net.ready) return fail(AZ_E_STATE, "az_engine_set_weights was not called");
-  if (int rc_ = enter(e)) return rc_;
+  AZ_TRY(e->enter());
   const int HW = e->g.HW, A = e->g.A, chunk = e->g.slots;
   for (int off = 0; off < n; off += chunk) {
     const int m = std::min(chunk, n - off);
@@ -959,9 +847,8 @@ int az_forward(az_engine* e, const float* x, int n, float* probs, float* values)
 
 int az_stats_get(az_engine* e, az_stats* st) {
   if (!e || !st) return fail(AZ_E_INVALID, "null argument");
-  AZ_HIP(hipSetDevice(e->device));
+  AZ_TRY(e->enter());
   int rc;
-  if ((rc = sync_all(e))) return rc;
   unsigned long long h[az::kStatCount];
   if ((rc = az::read_common_stats(st, h, e->t.stats, e->t.game_id, e->g.slots, e->cache)))
     return rc;
@@ -996,22 +883,20 @@ int az_stats_get(az_engine* e, az_stats* st) {
 int az_cache_enable(az_engine* e, int on) {
   if (!e) return fail(AZ_E_INVALID, "null engine");
   if (!e->cache.state) return on ? fail(AZ_E_STATE, "engine created with cache_log2 = 0") : 0;
-  int rc;
-  if ((rc = sync_all(e))) return rc;
+  AZ_TRY(e->enter());
   e->cache.enabled = on != 0;
   return 0;
 }
 
 int az_cache_clear(az_engine* e) {
   if (!e) return fail(AZ_E_INVALID, "null engine");
-  AZ_HIP(hipSetDevice(e->device));
+  AZ_TRY(e->enter());
   return cache_clear(e);
 }
 
 int az_timer_enable(az_engine* e, int on) {
   if (!e) return fail(AZ_E_INVALID, "null engine");
-  int rc;
-  if ((rc = sync_all(e))) return rc;
+  AZ_TRY(e->enter());
   // on: 1 = conv launches, 2 = conv + select/expand launches (more events per
   // simulation: bench.py times the tree kernels in a window of their own),
   // k >= 3 = every k-th conv launch of each lane (sampled)
@@ -1028,6 +913,7 @@ int az_timer_enable(az_engine* e, int on) {
 
 int az_pow_table(az_engine* e, double* out, int64_t n) {
   if (!e || !out || n < 0 || n > e->g.pow_len) return fail(AZ_E_INVALID, "bad arguments");
+  AZ_TRY(e->enter());
   AZ_HIP(hipMemcpy(out, e->t.powtab, n * sizeof(double), hipMemcpyDeviceToHost));
   return 0;
 }
@@ -1038,8 +924,7 @@ int az_selfplay_begin(az_engine* e, int64_t first_game, int64_t n_games, uint32_
   int rc;
   e->broken = false;  // every slot starts a fresh game
   if ((rc = ready_to_search(e))) return rc;
-  AZ_HIP(hipSetDevice(e->device));
-  if ((rc = sync_all(e))) return rc;  // moves of an earlier batch may still be running (async steps)
+  AZ_TRY(e->enter());  // moves of an earlier batch may still be running (async steps)
   e->samples.free_all();
   az::SampleDev& smp = e->smp;
   smp = az::SampleDev{};
@@ -1054,72 +939,50 @@ int az_selfplay_begin(az_engine* e, int64_t first_game, int64_t n_games, uint32_
       (rc = sb.alloc_zeroed_async(&smp.result, G, s)) || (rc = sb.alloc_zeroed_async(&smp.expansions, G, s)) ||
       (rc = sb.alloc_zeroed_async(&smp.done_ids, G, s)) || (rc = sb.alloc_zeroed_async(&smp.done_count, 1, s)))
     return rc;
-  e->clock.begin_batch();
-  unsigned long long st[az::kStatCount] = {0};
-  const int64_t first_wave = std::min<int64_t>(n_games, e->g.slots);
-  st[az::kStatNextGame] = (unsigned long long)(first_game + first_wave);
-  AZ_HIP(hipMemcpyAsync(e->t.stats, st, sizeof(st), hipMemcpyHostToDevice, e->stream));
-  az::launch_slot_init(e->g, e->t, smp, first_wave, e->stream);
-  AZ_HIP(hipGetLastError());
-  if (e->g.halves > 1)  // every slot starts with no chunk: the pools are empty
-    for (Lane* L : e->lanes) {
-      AZ_HIP(hipMemsetAsync(L->t.pool_top, 0, sizeof(unsigned long long), e->stream));
-      AZ_HIP(hipMemsetAsync(L->t.dst_top, 0, sizeof(unsigned long long), e->stream));
-    }
-  AZ_HIP(hipStreamSynchronize(e->stream));
-  e->sp_first = first_game;
-  e->sp_n = n_games;
-  return 0;
+  return e->begin_batch(e->t.stats, e->g.slots, first_game, n_games, [&](int64_t first_wave) {
+    az::launch_slot_init(e->g, e->t, smp, first_wave, e->stream);
+    AZ_HIP(hipGetLastError());
+    if (e->g.halves > 1)  // every slot starts with no chunk: the pools are empty
+      for (Lane* L : e->lanes) {
+        AZ_HIP(hipMemsetAsync(L->t.pool_top, 0, sizeof(unsigned long long), e->stream));
+        AZ_HIP(hipMemsetAsync(L->t.dst_top, 0, sizeof(unsigned long long), e->stream));
+      }
+    return 0;
+  });
 }
 
 int az_selfplay_step(az_engine* e, int n_moves, az_stats* st) {
   if (!e || n_moves < 0) return fail(AZ_E_INVALID, "bad arguments");
   int rc;
   if ((rc = ready_to_search(e))) return rc;
-  AZ_HIP(hipSetDevice(e->device));
-  for (int mv = 0; mv < n_moves; ++mv) {
-    const int64_t m = e->clock.issued++;
-    // lanes interleaved per simulation so every stream always has work queued
-    for (int s = 0; s < e->g.sims; ++s)
-      for (Lane* L : e->lanes)
-        if ((rc = simulate(e, *L))) return rc;
-    for (size_t l = 0; l < e->lanes.size(); ++l) {
-      Lane* L = e->lanes[l];
-      if ((rc = e->clock.before_play(m, l, L->stream))) return rc;
-      az::launch_play(L->g, L->t, e->smp, nullptr, -1, 0, 1, L->stream);
-      az::launch_compact(L->g, L->t, L->stream);
-      if (L->g.halves > 1) {  // the kept trees are in the other half now: it is the current one
-        std::swap(L->t.edges, L->t.dst_edges);
-        std::swap(L->t.pool_top, L->t.dst_top);
-      }
-      if ((rc = e->clock.after_play(m, l, L->stream, e->smp.done_count))) return rc;
-    }
-    AZ_HIP(hipGetLastError());
-  }
-  if (!st) return 0;  // asynchronous: the moves run on while the caller drains earlier ones
-  if ((rc = sync_all(e))) return rc;
+  rc = e->step_moves(
+      n_moves, e->g.sims, e->lanes, e->smp.done_count, [&](Lane& L) { return simulate(e, L); },
+      [](Lane&) { return 0; },
+      [&](Lane& L) {
+        az::launch_play(L.g, L.t, e->smp, nullptr, -1, 0, 1, L.stream);
+        az::launch_compact(L.g, L.t, L.stream);
+        if (L.g.halves > 1) {  // the kept trees are in the other half now: it is the current one
+          std::swap(L.t.edges, L.t.dst_edges);
+          std::swap(L.t.pool_top, L.t.dst_top);
+        }
+      });
+  if (rc || !st) return rc;  // st = NULL, asynchronous: the moves run on while the caller drains earlier ones
+  if ((rc = e->sync_all())) return rc;
   if ((rc = check_device_errors(e))) return rc;
   return az_stats_get(e, st);
 }
 
 int az_selfplay_run(az_engine* e, int64_t first_game, int64_t n_games, uint32_t base_seed,
                     az_stats* st) {
-  int rc;
-  if ((rc = az_selfplay_begin(e, first_game, n_games, base_seed))) return rc;
-  az_stats tmp;
-  for (;;) {
-    if ((rc = az_selfplay_step(e, 1, &tmp))) return rc;
-    if (tmp.active_slots == 0) break;
-  }
-  if (st) *st = tmp;
-  return 0;
+  return az::run_to_end(
+      st, [&] { return az_selfplay_begin(e, first_game, n_games, base_seed); },
+      [&](az_stats* now) { return az_selfplay_step(e, 1, now); });
 }
 
 int az_selfplay_results(az_engine* e, int32_t* lengths, int32_t* results, int32_t* expansions,
                         int8_t* boards, double* policies, int32_t* moves) {
   if (!e) return fail(AZ_E_INVALID, "null engine");
-  if (int rc_ = enter(e)) return rc_;
-  AZ_HIP(hipStreamSynchronize(e->stream));
+  AZ_TRY(e->enter());
   const size_t G = (size_t)e->sp_n, P = (size_t)e->g.HW, A = (size_t)e->g.A, HW = (size_t)e->g.HW;
   if (G == 0) return 0;
   const az::SampleDev& smp = e->smp;
@@ -1190,7 +1053,7 @@ int az_selfplay_drain(az_engine* e, int64_t max_games, int64_t* n_out, int64_t* 
 // ------------------------------------------------------------------ tree API
 int az_tree_reset(az_engine* e, int n, const int32_t* slots, const int8_t* boards) {
   if (!e || n < 0 || n > e->g.slots || (n && (!slots || !boards))) return fail(AZ_E_INVALID, "bad arguments");
-  if (int rc_ = enter(e)) return rc_;
+  AZ_TRY(e->enter());
   if (int rc_ = tree_api_ok(e)) return rc_;
   std::vector<az::Board> hb(n);
   for (int i = 0; i < n; ++i) {
@@ -1209,7 +1072,7 @@ int az_tree_reset(az_engine* e, int n, const int32_t* slots, const int8_t* board
 
 int az_tree_release(az_engine* e, int n, const int32_t* slots) {
   if (!e || n < 0 || n > e->g.slots || (n && !slots)) return fail(AZ_E_INVALID, "bad arguments");
-  if (int rc_ = enter(e)) return rc_;
+  AZ_TRY(e->enter());
   for (int i = 0; i < n; ++i)
     if (slots[i] < 0 || slots[i] >= e->g.slots) return fail(AZ_E_INVALID, "slot out of range");
   AZ_HIP(hipMemcpyAsync(e->dev_i32, slots, n * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
@@ -1226,7 +1089,7 @@ int az_tree_search(az_engine* e, int n_sims) {
                               "(the caller's np.random.dirichlet draws)");
   int rc;
   if ((rc = ready_to_search(e))) return rc;
-  if (int rc_ = enter(e)) return rc_;
+  AZ_TRY(e->enter());
   if (int rc_ = tree_api_ok(e)) return rc_;
   for (int s = 0; s < n_sims; ++s)
     if ((rc = simulate(e, e->whole))) return rc;
@@ -1240,7 +1103,7 @@ int az_tree_search_noise(az_engine* e, int n_sims, const double* noise, int rows
     return fail(AZ_E_INVALID, "az_tree_search_noise needs an engine created with dirichlet_noise = 1");
   int rc;
   if ((rc = ready_to_search(e))) return rc;
-  if (int rc_ = enter(e)) return rc_;
+  AZ_TRY(e->enter());
   if (int rc_ = tree_api_ok(e)) return rc_;
   const size_t S = (size_t)e->g.slots, n = S * (size_t)std::max(rows, 1) * e->g.A;
   az::TreeDev& t = e->whole.t;
@@ -1269,7 +1132,7 @@ int az_tree_play(az_engine* e, const double* uniforms, int greedy, int determini
                  int32_t* moves, int32_t* status, double* policy) {
   if (!e || (!deterministic && !uniforms)) return fail(AZ_E_INVALID, "bad arguments");
   if (e->broken) return ready_to_search(e);
-  if (int rc_ = enter(e)) return rc_;
+  AZ_TRY(e->enter());
   if (int rc_ = tree_api_ok(e)) return rc_;
   const size_t S = (size_t)e->g.slots;
   if (!deterministic)
@@ -1289,8 +1152,7 @@ int az_tree_play(az_engine* e, const double* uniforms, int greedy, int determini
 
 int az_tree_info(az_engine* e, int slot, int64_t* info, float* root_value) {
   if (!e || !info || slot < 0 || slot >= e->g.slots) return fail(AZ_E_INVALID, "bad arguments");
-  if (int rc_ = enter(e)) return rc_;
-  AZ_HIP(hipStreamSynchronize(e->stream));
+  AZ_TRY(e->enter());
   int32_t top, first, cnt, ply;
   int64_t gid;
   AZ_HIP(hipMemcpy(&top, e->t.arena_top + slot, 4, hipMemcpyDeviceToHost));
@@ -1310,8 +1172,7 @@ int az_tree_info(az_engine* e, int slot, int64_t* info, float* root_value) {
 int az_tree_export(az_engine* e, int slot, double* prior, double* w, int32_t* n, int32_t* child,
                    int32_t* child_n, int32_t* action, float* child_value) {
   if (!e || slot < 0 || slot >= e->g.slots) return fail(AZ_E_INVALID, "bad arguments");
-  if (int rc_ = enter(e)) return rc_;
-  AZ_HIP(hipStreamSynchronize(e->stream));
+  AZ_TRY(e->enter());
   if (int rc_ = tree_api_ok(e)) return rc_;
   int32_t top;
   AZ_HIP(hipMemcpy(&top, e->t.arena_top + slot, 4, hipMemcpyDeviceToHost));

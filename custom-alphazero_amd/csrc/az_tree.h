@@ -41,8 +41,9 @@ enum : int {
   kStatPoolHigh = 12 * kStatStride,    // pooled arenas: most edges a lane's half held at a move's end (atomicMax)
   kStatCount = 13 * kStatStride        // words (kStatCacheInserts counts since engine creation; CacheDev::ctl since a clear)
 };
-// a lane's per-simulation queue counters (eval, miss, nn, dup), one block per
-// simulation parity, each counter on a 128-byte line of its own
+// a lane's per-simulation queue counters (eval, miss, nn; the block's fourth
+// counter went with the per-simulation dedup), one block per simulation
+// parity, each counter on a 128-byte line of its own
 constexpr int kCountStride = 32;
 constexpr int kCountWords = 2 * 4 * kCountStride;
 enum : unsigned long long {

@@ -268,8 +268,124 @@ def tensor_array(named):
     return arr, len(items), keep
 
 
-class Engine:
+class _EngineBase:
+    """What Engine and ChessEngine share: the handle's life, weights, the host
+    evaluator's trampoline, the self-play calls and the chunked drain loop.
+    _ABI is the class's prefix of the libaz symbols, _STATS its stats symbol."""
+
+    _ABI = _STATS = None
+
+    def _call(self, name, *args):
+        return getattr(self._L, self._ABI + name)(self._h, *args)
+
+    def _attach(self, handle, L):
+        self._h, self._L, self._n_games = handle, L, 0
+        self._host_fn = None     # the EVAL_FN object (kept alive while the engine may call it)
+        self._host_error = None  # an exception the host evaluator raised inside a search
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._call("engine_destroy")
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # pragma: no cover - interpreter teardown
+            pass
+
+    def set_weights(self, named):
+        """named: iterable of (name, array-like or torch tensor)."""
+        arr, n, _keep = tensor_array(named)
+        _check(self._call("engine_set_weights", arr, n))
+
+    def _set_host_evaluator(self, fn, row_shape, actions, strict):
+        """fn(x [n, *row_shape]) -> (probs [n, actions], values [n] or [n, 1]) as
+        the engine's az_eval_fn.  strict: outputs of any other shape raise
+        ValueError; otherwise they are reshaped."""
+        A = actions
+
+        def cb(_user, xp, n, pp, vp):
+            try:
+                x = np.ctypeslib.as_array(xp, shape=(n,) + row_shape).copy()
+                p, v = fn(x)
+                p = _as_numpy(p).astype(np.float32, copy=False)
+                v = _as_numpy(v).astype(np.float32, copy=False)
+                if strict and p.shape != (n, A):
+                    raise ValueError(f"the host evaluator returned probs of shape {p.shape}, expected {(n, A)}")
+                if strict and v.shape not in ((n,), (n, 1)):
+                    raise ValueError(f"the host evaluator returned values of shape {v.shape}, "
+                                     f"expected {(n,)} or {(n, 1)}")
+                np.ctypeslib.as_array(pp, shape=(n, A))[:] = p.reshape(n, A)
+                np.ctypeslib.as_array(vp, shape=(n,))[:] = v.reshape(n)
+                return 0
+            except BaseException as ex:  # noqa: BLE001 - handed back to the caller below
+                self._host_error = ex
+                return 1
+
+        host_fn = EVAL_FN(cb)
+        _check(self._call("engine_set_evaluator", host_fn, None))
+        self._host_fn = host_fn
+
+    def _search_call(self, rc):
+        """_check for calls that can run the host evaluator: its exception first."""
+        if self._host_error is not None:
+            ex, self._host_error = self._host_error, None
+            raise ex
+        _check(rc)
+
+    def selfplay_begin(self, first_game, n_games, base_seed):
+        _check(self._call("selfplay_begin", int(first_game), int(n_games), int(base_seed) & 0xFFFFFFFF))
+        self._n_games = int(n_games)
+
+    def selfplay_step(self, n_moves=1, sync=True):
+        """Enqueue n_moves moves for every slot.  sync=False returns at once
+        (no stats): the moves run while the caller drains earlier ones --
+        selfplay_drain then returns the games of the newest move whose
+        snapshot is complete and waits at most for the move before the
+        running one (*_selfplay_step with st = NULL)."""
+        st = Stats() if sync else None
+        self._search_call(self._call("selfplay_step", int(n_moves), ctypes.byref(st) if sync else None))
+        return st.as_dict() if sync else None
+
+    def selfplay_run(self, first_game, n_games, base_seed):
+        st = Stats()
+        self._search_call(self._call("selfplay_run", int(first_game), int(n_games), int(base_seed) & 0xFFFFFFFF,
+                                     ctypes.byref(st)))
+        self._n_games = int(n_games)
+        return st.as_dict()
+
+    def _drain(self, max_games, chunk, buffers):
+        """The drain loop: buffers(G) makes the out arrays for G games, keyed in
+        the order *_selfplay_drain takes them.  Drained in chunks of `chunk`
+        games, so a call allocates for what it returns, not for the whole batch."""
+        left = int(max_games if max_games is not None else max(self._n_games, 1))
+        parts = []
+        while left > 0:
+            G = min(chunk, left)
+            n = ctypes.c_int64(0)
+            out = buffers(G)
+            _check(self._call("selfplay_drain", G, ctypes.byref(n), *(_ptr(v) for v in out.values())))
+            k = int(n.value)
+            parts.append({key: v[:k] for key, v in out.items()} if k < G else out)
+            left -= k
+            if k < G:
+                break
+        if len(parts) == 1:
+            p = parts[0]
+            return {key: (v.copy() if v.base is not None else v) for key, v in p.items()}
+        return {key: np.concatenate([p[key] for p in parts]) for key in parts[0]}
+
+    def stats(self):
+        st = Stats()
+        _check(getattr(self._L, self._STATS)(self._h, ctypes.byref(st)))
+        return st.as_dict()
+
+
+class Engine(_EngineBase):
     """One libaz engine: one device, one HIP stream, `slots` concurrent trees."""
+
+    _ABI, _STATS = "az_", "az_stats_get"
 
     def __init__(self, height=6, width=7, n=4, gravity=True, mcts_iterations=100, slots=1,
                  evaluator=EVAL_NETWORK, index_move_greedy=8, exploration_constant=1.5,
@@ -304,33 +420,12 @@ class Engine:
                      rng_skip=2 * height * width * 4 if rng_skip is None else int(rng_skip))
         handle = ctypes.c_void_p()
         _check(L.az_engine_create(int(device), ctypes.byref(cfg), ctypes.byref(handle)))
-        self._h = handle
-        self._L = L
-        self._n_games = 0
-        self._host_fn = None     # the EVAL_FN object (kept alive while the engine may call it)
-        self._host_error = None  # an exception the host evaluator raised inside a search
+        self._attach(handle, L)
 
     @property
     def lanes(self):
         """The slot groups (streams) the engine runs (az_engine_lanes)."""
         return int(self._L.az_engine_lanes(self._h))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.az_engine_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # pragma: no cover - interpreter teardown
-            pass
-
-    # ------------------------------------------------------------- weights
-    def set_weights(self, named):
-        """named: iterable of (name, array-like or torch tensor)."""
-        arr, n, _keep = tensor_array(named)
-        _check(self._L.az_engine_set_weights(self._h, arr, n))
 
     def set_host_evaluator(self, fn):
         """EVAL_HOST engines: fn(x) with x [n, H, W, 4] float32 full_state planes
@@ -339,30 +434,7 @@ class Engine:
         every leaf that needs an evaluation.  Outputs may be numpy arrays or
         torch / TF tensors.  An exception inside fn ends the search and is
         re-raised by the call that ran it."""
-        H, W, A = self.height, self.width, self.action_space
-
-        def cb(_user, xp, n, pp, vp):
-            try:
-                x = np.ctypeslib.as_array(xp, shape=(n, H, W, 4)).copy()
-                p, v = fn(x)
-                p = _as_numpy(p).astype(np.float32, copy=False).reshape(n, A)
-                v = _as_numpy(v).astype(np.float32, copy=False).reshape(n)
-                np.ctypeslib.as_array(pp, shape=(n, A))[:] = p
-                np.ctypeslib.as_array(vp, shape=(n,))[:] = v
-                return 0
-            except BaseException as ex:  # noqa: BLE001 - handed back to the caller below
-                self._host_error = ex
-                return 1
-
-        self._host_fn = EVAL_FN(cb)
-        _check(self._L.az_engine_set_evaluator(self._h, self._host_fn, None))
-
-    def _search_call(self, rc):
-        """_check for calls that can run the host evaluator: its exception first."""
-        if self._host_error is not None:
-            ex, self._host_error = self._host_error, None
-            raise ex
-        _check(rc)
+        self._set_host_evaluator(fn, (self.height, self.width, 4), self.action_space, strict=False)
 
     # ------------------------------------------------------------- eval
     def encode(self, boards):
@@ -380,31 +452,6 @@ class Engine:
         return probs, values
 
     # ------------------------------------------------------------- self-play
-    def selfplay_begin(self, first_game, n_games, base_seed):
-        _check(self._L.az_selfplay_begin(self._h, int(first_game), int(n_games),
-                                         int(base_seed) & 0xFFFFFFFF))
-        self._n_games = int(n_games)
-
-    def selfplay_step(self, n_moves=1, sync=True):
-        """Enqueue n_moves moves for every slot.  sync=False returns at once
-        (no stats): the moves run while the caller drains earlier ones --
-        selfplay_drain then returns the games of the newest move whose
-        snapshot is complete and waits at most for the move before the
-        running one (az_selfplay_step with st = NULL)."""
-        if not sync:
-            self._search_call(self._L.az_selfplay_step(self._h, int(n_moves), None))
-            return None
-        st = Stats()
-        self._search_call(self._L.az_selfplay_step(self._h, int(n_moves), ctypes.byref(st)))
-        return st.as_dict()
-
-    def selfplay_run(self, first_game, n_games, base_seed):
-        st = Stats()
-        self._search_call(self._L.az_selfplay_run(self._h, int(first_game), int(n_games),
-                                                  int(base_seed) & 0xFFFFFFFF, ctypes.byref(st)))
-        self._n_games = int(n_games)
-        return st.as_dict()
-
     def selfplay_results(self):
         G, P, A = self._n_games, self.height * self.width, self.action_space
         lengths = np.zeros(G, np.int32)
@@ -421,30 +468,14 @@ class Engine:
     def selfplay_drain(self, max_games=None, chunk=4096):
         """Games finished since the previous drain, copied to the host (the
         samples of a running batch, az_selfplay_drain): dict of arrays with
-        a leading game axis plus `game_ids` (finish order).  Drained in
-        chunks of `chunk` games, so a call allocates for what it returns, not
-        for the whole batch."""
-        left = int(max_games if max_games is not None else max(self._n_games, 1))
+        a leading game axis plus `game_ids` (finish order), in chunks of
+        `chunk` games."""
         P, A = self.height * self.width, self.action_space
-        parts = []
-        while left > 0:
-            G = min(chunk, left)
-            n = ctypes.c_int64(0)
-            out = dict(game_ids=np.zeros(G, np.int64), lengths=np.zeros(G, np.int32),
-                       results=np.zeros(G, np.int32), expansions=np.zeros(G, np.int32),
-                       boards=np.zeros((G, P, self.height, self.width), np.int8),
-                       policies=np.zeros((G, P, A), np.float64), moves=np.zeros((G, P), np.int32))
-            _check(self._L.az_selfplay_drain(self._h, G, ctypes.byref(n), *(_ptr(out[k]) for k in (
-                "game_ids", "lengths", "results", "expansions", "boards", "policies", "moves"))))
-            k = int(n.value)
-            parts.append({key: v[:k] for key, v in out.items()} if k < G else out)
-            left -= k
-            if k < G:
-                break
-        if len(parts) == 1:
-            p = parts[0]
-            return {key: (v.copy() if v.base is not None else v) for key, v in p.items()}
-        return {key: np.concatenate([p[key] for p in parts]) for key in parts[0]}
+        return self._drain(max_games, chunk, lambda G: dict(
+            game_ids=np.zeros(G, np.int64), lengths=np.zeros(G, np.int32),
+            results=np.zeros(G, np.int32), expansions=np.zeros(G, np.int32),
+            boards=np.zeros((G, P, self.height, self.width), np.int8),
+            policies=np.zeros((G, P, A), np.float64), moves=np.zeros((G, P), np.int32)))
 
     # ------------------------------------------------------------- tree API
     def tree_reset(self, slots, boards):
@@ -505,11 +536,6 @@ class Engine:
         return out
 
     # ------------------------------------------------------------- misc
-    def stats(self):
-        st = Stats()
-        _check(self._L.az_stats_get(self._h, ctypes.byref(st)))
-        return st.as_dict()
-
     def cache_clear(self):
         _check(self._L.az_cache_clear(self._h))
 
@@ -807,7 +833,7 @@ class Solver:
         return scores, status, nodes
 
 
-class ChessEngine:
+class ChessEngine(_EngineBase):
     """libaz chess self-play engine (include/az_chess.h): `slots` concurrent
     chess games on one device, MCTS with the policy/value network on the
     (8, 8, 118) Board.full_state planes and the 1880-move action space -- or,
@@ -820,6 +846,7 @@ class ChessEngine:
 
     ACTIONS = 1880
     MAX_MOVES = 256
+    _ABI, _STATS = "az_chess_", "az_chess_stats"
 
     def __init__(self, mcts_iterations=800, slots=256, evaluator=EVAL_NETWORK, max_plies=512,
                  index_move_greedy=8, exploration_constant=1.5, filters=128, depth=4,
@@ -838,24 +865,7 @@ class ChessEngine:
                           dirichlet_ratio=float(dirichlet_ratio))
         handle = ctypes.c_void_p()
         _check(L.az_chess_engine_create(int(device), ctypes.byref(cfg), ctypes.byref(handle)))
-        self._h, self._L, self._n_games = handle, L, 0
-        self._host_fn = None     # the EVAL_FN object (kept alive while the engine may call it)
-        self._host_error = None  # an exception the host evaluator raised inside a search
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.az_chess_engine_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # pragma: no cover
-            pass
-
-    def set_weights(self, named):
-        arr, n, _keep = tensor_array(named)
-        _check(self._L.az_chess_engine_set_weights(self._h, arr, n))
+        self._attach(handle, L)
 
     def set_host_evaluator(self, fn):
         """EVAL_HOST engines: fn(x) with x [n, 8, 8, 118] float32 (Board.full_state
@@ -865,36 +875,7 @@ class ChessEngine:
         (az_chess_engine_set_evaluator).  Outputs may be numpy arrays or torch
         / TF tensors; a wrong shape raises ValueError.  An exception inside fn
         ends the search and is re-raised by the call that ran it."""
-        A = self.ACTIONS
-
-        def cb(_user, xp, n, pp, vp):
-            try:
-                x = np.ctypeslib.as_array(xp, shape=(n, 8, 8, 118)).copy()
-                p, v = fn(x)
-                p = _as_numpy(p).astype(np.float32, copy=False)
-                v = _as_numpy(v).astype(np.float32, copy=False)
-                if p.shape != (n, A):
-                    raise ValueError(f"the host evaluator returned probs of shape {p.shape}, expected {(n, A)}")
-                if v.shape not in ((n,), (n, 1)):
-                    raise ValueError(f"the host evaluator returned values of shape {v.shape}, "
-                                     f"expected {(n,)} or {(n, 1)}")
-                np.ctypeslib.as_array(pp, shape=(n, A))[:] = p
-                np.ctypeslib.as_array(vp, shape=(n,))[:] = v.reshape(n)
-                return 0
-            except BaseException as ex:  # noqa: BLE001 - handed back to the caller below
-                self._host_error = ex
-                return 1
-
-        host_fn = EVAL_FN(cb)
-        _check(self._L.az_chess_engine_set_evaluator(self._h, host_fn, None))
-        self._host_fn = host_fn
-
-    def _search_call(self, rc):
-        """_check for calls that can run the host evaluator: its exception first."""
-        if self._host_error is not None:
-            ex, self._host_error = self._host_error, None
-            raise ex
-        _check(rc)
+        self._set_host_evaluator(fn, (8, 8, 118), self.ACTIONS, strict=True)
 
     def forward(self, x):
         x = np.ascontiguousarray(x, np.float32).reshape(-1, 8, 8, 118)
@@ -903,56 +884,19 @@ class ChessEngine:
         _check(self._L.az_chess_forward(self._h, _ptr(x), len(x), _ptr(probs), _ptr(values)))
         return probs, values
 
-    def selfplay_begin(self, first_game, n_games, base_seed):
-        _check(self._L.az_chess_selfplay_begin(self._h, int(first_game), int(n_games),
-                                               int(base_seed) & 0xFFFFFFFF))
-        self._n_games = int(n_games)
-
-    def selfplay_step(self, n_moves=1, sync=True):
-        """Enqueue n_moves moves for every slot; sync=False returns at once (no
-        stats) and selfplay_drain returns the games of the newest move whose
-        snapshot is complete (az_chess_selfplay_step with st = NULL, ABI 10)."""
-        if not sync:
-            self._search_call(self._L.az_chess_selfplay_step(self._h, int(n_moves), None))
-            return None
-        st = Stats()
-        self._search_call(self._L.az_chess_selfplay_step(self._h, int(n_moves), ctypes.byref(st)))
-        return st.as_dict()
-
     def selfplay_drain(self, max_games=None, chunk=64):
         """Games finished since the previous drain (az_chess_selfplay_drain):
         the arrays of selfplay_results with a leading axis over the drained
         games in finish order, plus `game_ids`.  Chunked: a chess game's dense
         rows are ~1.3 MB (max_plies x 256 policy entries)."""
         from custom_alphazero.chess.kernels import POS_DTYPE
-        left = int(max_games if max_games is not None else max(self._n_games, 1))
         P, M = self.max_plies, self.MAX_MOVES
-        keys = ("game_ids", "lengths", "results", "terminations", "expansions", "positions", "moves",
-                "policy_n", "policy_actions", "policy_probs")
-        parts = []
-        while left > 0:
-            G = min(chunk, left)
-            n = ctypes.c_int64(0)
-            out = dict(game_ids=np.zeros(G, np.int64), lengths=np.zeros(G, np.int32),
-                       results=np.zeros(G, np.int32), terminations=np.zeros(G, np.int32),
-                       expansions=np.zeros(G, np.int32), positions=np.zeros((G, P), POS_DTYPE),
-                       moves=np.zeros((G, P), np.uint16), policy_n=np.zeros((G, P), np.int32),
-                       policy_actions=np.zeros((G, P, M), np.int16),
-                       policy_probs=np.zeros((G, P, M), np.float64))
-            _check(self._L.az_chess_selfplay_drain(self._h, G, ctypes.byref(n), *(_ptr(out[k]) for k in keys)))
-            k = int(n.value)
-            parts.append({key: v[:k].copy() for key, v in out.items()})
-            left -= k
-            if k < G:
-                break
-        return {key: np.concatenate([p[key] for p in parts]) for key in keys}
-
-    def selfplay_run(self, first_game, n_games, base_seed):
-        st = Stats()
-        self._search_call(self._L.az_chess_selfplay_run(self._h, int(first_game), int(n_games),
-                                                        int(base_seed) & 0xFFFFFFFF, ctypes.byref(st)))
-        self._n_games = int(n_games)
-        return st.as_dict()
+        return self._drain(max_games, chunk, lambda G: dict(
+            game_ids=np.zeros(G, np.int64), lengths=np.zeros(G, np.int32),
+            results=np.zeros(G, np.int32), terminations=np.zeros(G, np.int32),
+            expansions=np.zeros(G, np.int32), positions=np.zeros((G, P), POS_DTYPE),
+            moves=np.zeros((G, P), np.uint16), policy_n=np.zeros((G, P), np.int32),
+            policy_actions=np.zeros((G, P, M), np.int16), policy_probs=np.zeros((G, P, M), np.float64)))
 
     def selfplay_results(self, with_samples=True):
         from custom_alphazero.chess.kernels import POS_DTYPE
@@ -970,11 +914,6 @@ class ChessEngine:
             _ptr(g("expansions")), _ptr(g("positions")), _ptr(g("moves")), _ptr(g("policy_n")),
             _ptr(g("policy_actions")), _ptr(g("policy_probs"))))
         return out
-
-    def stats(self):
-        st = Stats()
-        _check(self._L.az_chess_stats(self._h, ctypes.byref(st)))
-        return st.as_dict()
 
     def timer(self, on):
         _check(self._L.az_chess_timer_enable(self._h, int(bool(on))))

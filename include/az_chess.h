@@ -191,7 +191,9 @@ int az_chess_selfplay_begin(az_chess_engine* eng, int64_t first_game, int64_t n_
                             uint32_t base_seed);
 /* With st = NULL the moves are only enqueued (ABI 10): the call returns at once
  * and device errors surface at the next synchronizing call; with st it waits
- * for them and fills the stats. */
+ * for them and fills the stats.  Only this call and az_chess_selfplay_drain
+ * run beside the queued moves: every other call on the engine, az_chess_forward
+ * included, first waits for them. */
 int az_chess_selfplay_step(az_chess_engine* eng, int n_moves, az_stats* st);
 int az_chess_selfplay_run(az_chess_engine* eng, int64_t first_game, int64_t n_games,
                           uint32_t base_seed, az_stats* st);
