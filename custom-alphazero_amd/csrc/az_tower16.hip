@@ -194,6 +194,13 @@ __device__ __forceinline__ float wmax(float v) {
   return wreduce(v, [](float a, float b) { return fmaxf(a, b); });
 }
 
+// n / d for 0 <= n < 2^16 and an integer d >= 1 (exact as a float: d < 2^24) from
+// rd = v_rcp_f32(d) (1 ulp), in four instructions instead of the ~30 of an integer division.
+// (n + 0.5) / d is at least 0.5 / d from an integer and the product's error is below
+// n * 2^-21 / d, so the truncation is exact whenever n < 2^20: the bound is on n alone
+// (the uses: thread and row indices below 2^12)
+__device__ __forceinline__ int div_small(int n, float rd) { return (int)(((float)n + 0.5f) * rd); }
+
 // smallest s >= 0 with m * 2^-s <= kRange (m >= 0, finite)
 __device__ __forceinline__ int range_exp(float m) {
   int s = 0;
@@ -807,32 +814,45 @@ __device__ __forceinline__ void tower16_tile(const TowerNet* __restrict__ net, c
 #pragma unroll
         for (int i = 0; i < SG; ++i) {
           const int mb = g0 + i;
-          float v[8];
+          const int py = (yx[mb] >> 8) & 255, px = yx[mb] & 255;
+          uint4 a0, a1;
+          if (boards) {
+            // the one-hot planes as fp16 bits (1.0 = 0x3c00), no float on the way: the words
+            // split_u8 makes of {0, 1} floats -- t0 the planes themselves, t1 = +0 (x - t0 exact)
+            uint32_t wd[2][2];
 #pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            const int t = 8 * ks + 2 * gq + h;  // tap of k = 32 ks + 8 gq + 4 h + plane
-            const int dy = t / 3 - 1, dx = t - (t / 3) * 3 - 1;
-            const int py = (yx[mb] >> 8) & 255, px = yx[mb] & 255;
-            const bool ok = t < 9 && py + dy >= 0 && py + dy < H && px + dx >= 0 && px + dx < W;
-            float4 pl = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (ok) {
-              const int q = (py + dy) * W + px + dx;
-              if (boards) {
-                const uint64_t ow = q < 64 ? bd[i].own[0] : bd[i].own[1],
-                               op = q < 64 ? bd[i].opp[0] : bd[i].opp[1];
-                const bool o = (ow >> (q & 63)) & 1ull, e = (op >> (q & 63)) & 1ull;
-                pl = make_float4(o || e ? 0.f : 1.f, o ? 1.f : 0.f, e ? 1.f : 0.f, 1.f);
-              } else {
-                pl = gld(x + (size_t)(b0 + (yx[mb] >> 16)) * HW + q);
+            for (int h = 0; h < 2; ++h) {
+              wd[h][0] = wd[h][1] = 0u;
+              if (ks == 1 && h == 1) continue;  // taps 9 + 2 gq: past the nine
+              const int t = 8 * ks + 2 * gq + h;  // tap of k = 32 ks + 8 gq + 4 h + plane
+              const int dy = t / 3 - 1, dx = t - (t / 3) * 3 - 1;
+              const int qy = py + dy, qx = px + dx, q = qy * W + qx;
+              const bool ok = t < 9 && (unsigned)qy < (unsigned)H && (unsigned)qx < (unsigned)W;
+              const uint64_t ow = q < 64 ? bd[i].own[0] : bd[i].own[1], op = q < 64 ? bd[i].opp[0] : bd[i].opp[1];
+              const uint32_t o = (uint32_t)(ow >> (q & 63)) & 1u, e = (uint32_t)(op >> (q & 63)) & 1u;
+              if (ok) {
+                wd[h][0] = ((o | e) ? 0u : 0x3c00u) | (o ? 0x3c000000u : 0u);  // (empty, own)
+                wd[h][1] = (e ? 0x3c00u : 0u) | 0x3c000000u;                   // (opp, 1)
               }
             }
-            v[4 * h + 0] = pl.x;
-            v[4 * h + 1] = pl.y;
-            v[4 * h + 2] = pl.z;
-            v[4 * h + 3] = pl.w;
+            a0 = make_uint4(wd[0][0], wd[0][1], wd[1][0], wd[1][1]);
+            a1 = make_uint4(0u, 0u, 0u, 0u);
+          } else {
+            float v[8];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+              const int t = 8 * ks + 2 * gq + h;
+              const int dy = t / 3 - 1, dx = t - (t / 3) * 3 - 1;
+              const bool ok = t < 9 && py + dy >= 0 && py + dy < H && px + dx >= 0 && px + dx < W;
+              float4 pl = make_float4(0.f, 0.f, 0.f, 0.f);
+              if (ok) pl = gld(x + (size_t)(b0 + (yx[mb] >> 16)) * HW + (py + dy) * W + px + dx);
+              v[4 * h + 0] = pl.x;
+              v[4 * h + 1] = pl.y;
+              v[4 * h + 2] = pl.z;
+              v[4 * h + 3] = pl.w;
+            }
+            split_u8(v, a0, a1);
           }
-          uint4 a0, a1;
-          split_u8(v, a0, a1);
           // t1*B0 + t0*b1 + t0*B0 per N block, as the K loop's k-step
 #pragma unroll
           for (int nb = 0; nb < 2; ++nb) {
@@ -875,6 +895,10 @@ __device__ __forceinline__ void tower16_tile(const TowerNet* __restrict__ net, c
 
   // ---------------------------------------------------------------- tower
   const int depth = T.depth;
+  // the heads' blob offsets, read here: behind the K loops' asm (a "memory"
+  // clobber) each would be a scalar round trip of its own in the heads' chain
+  const int off_b2 = T.off_b2, off_wpc = T.off_wpc, off_wvc = T.off_wvc, off_hb = T.off_hb, off_bpd = T.off_bpd,
+            off_bv1 = T.off_bv1, off_wv2 = T.off_wv2, off_wpd = T.off_wpd, off_wv1 = T.off_wv1;
   for (int d = 0; d < depth; ++d) {
 #pragma unroll
     for (int mb = 0; mb < MBW; ++mb)
@@ -924,6 +948,7 @@ __device__ __forceinline__ void tower16_tile(const TowerNet* __restrict__ net, c
         }
       }
     };
+    const float osc = T.s2[d];  // (before the K loop, as above)
     T16_WSTAMP(d, 2);
     if constexpr (DB) {
       // conv2: the 1x1 projection residual from X's rows, then (once every
@@ -938,8 +963,8 @@ __device__ __forceinline__ void tower16_tile(const TowerNet* __restrict__ net, c
         // (the blob pads wv1 to whole uint4s, and so does its staged place: HW * J need be no
         // multiple of 4 for the late copy -- hidden 1 or 255; the X tile takes multiples only)
         if (wv1x)
-          dma_to_lds<NT>(reinterpret_cast<uint4*>(wv1_xt ? reinterpret_cast<float*>(bufX) + TR * 48 : blob + T.off_wv1),
-                         T.blob + T.off_wv1, (HW * J + 3) / 4, wave, lane);
+          dma_to_lds<NT>(reinterpret_cast<uint4*>(wv1_xt ? reinterpret_cast<float*>(bufX) + TR * 48 : blob + off_wv1),
+                         T.blob + off_wv1, (HW * J + 3) / 4, wave, lane);
       };
 #pragma unroll
       for (int mb = 0; mb < MBW; ++mb)
@@ -955,8 +980,7 @@ __device__ __forceinline__ void tower16_tile(const TowerNet* __restrict__ net, c
     T16_WSTAMP(d, 3);
     if (d < 4) T16_STAMP(4 + 4 * d);
     if (d < 4) T16_STAMP4(26 + 4 * d);
-    const float osc = T.s2[d];
-    const float* bb = blob + T.off_b2 + d * 128;
+    const float* bb = blob + off_b2 + d * 128;
     if (d + 1 < depth) {
       if (!dbuf) __syncthreads();  // in place: every wave is done reading H
 #pragma unroll
@@ -988,8 +1012,8 @@ __device__ __forceinline__ void tower16_tile(const TowerNet* __restrict__ net, c
       __syncthreads();
       red = reinterpret_cast<float*>(act);
     }
-    const float* wpc = blob + T.off_wpc;
-    const float* wvc = blob + T.off_wvc;
+    const float* wpc = blob + off_wpc;
+    const float* wvc = blob + off_wvc;
     int hr[MBW], hyx[MBW], hb[MBW];  // laundered (see k_loop): addresses recomputed here, not hoisted and spilled
 #pragma unroll
     for (int mb = 0; mb < MBW; ++mb) {
@@ -1054,7 +1078,7 @@ __device__ __forceinline__ void tower16_tile(const TowerNet* __restrict__ net, c
     // per pixel (policy 0, policy 1, value) = 16 partials in order + folded
     // bias, ReLU: the dense heads read them (az_nn.hip policy_dense_kernel,
     // heads_tail_kernel)
-    const float* hbias = blob + T.off_hb;
+    const float* hbias = blob + off_hb;
     const float bpc0 = hbias[0], bpc1 = hbias[1], bvc0 = hbias[2];
     for (int rr = tid; rr < live; rr += NT) {
       const float* q = red + rr * 48;
@@ -1074,7 +1098,10 @@ __device__ __forceinline__ void tower16_tile(const TowerNet* __restrict__ net, c
   // and, pixel-major for the value dense's reads, vf [HW][8 boards]; logits
   // lg [bpw][A], policy partials pp [NT], value partials vp [bpw][P][J],
   // value hidden units hv [bpw][J]
-  const int P = NT / J;
+  // the heads' index arithmetic by reciprocals (div_small)
+  const float rHW = __builtin_amdgcn_rcpf((float)HW), rA = __builtin_amdgcn_rcpf((float)A),
+              rJ = __builtin_amdgcn_rcpf((float)J);
+  const int P = div_small(NT, rJ);
   float* pf = dbuf ? reinterpret_cast<float*>(bufH) : red + TR * 48;
   float* vf = pf + ((bpw * 2 * HW + 3) & ~3);  // 16-byte aligned
   float* lg = vf + kTowerMaxBoards * HW;
@@ -1082,7 +1109,7 @@ __device__ __forceinline__ void tower16_tile(const TowerNet* __restrict__ net, c
   float* vp = pp + NT;
   float* hv = vp + bpw * P * J;
   {
-    const float* hbias = blob + T.off_hb;
+    const float* hbias = blob + off_hb;
     const float bpc0 = hbias[0], bpc1 = hbias[1], bvc0 = hbias[2];
     for (int i = tid; i < 3 * live; i += NT) {  // (pixel row, output) pairs; 16 partials in order
       const int rr = i / 3, k = i - 3 * rr;
@@ -1090,7 +1117,7 @@ __device__ __forceinline__ void tower16_tile(const TowerNet* __restrict__ net, c
       float t = 0.f;
 #pragma unroll
       for (int j = 0; j < 16; ++j) t += q[3 * j];
-      const int b = rr / HW, p = rr - b * HW;
+      const int b = div_small(rr, rHW), p = rr - b * HW;
       if (k < 2) pf[b * 2 * HW + 2 * p + k] = fmaxf(t + (k ? bpc1 : bpc0), 0.f);
       else vf[p * kTowerMaxBoards + b] = fmaxf(t + bvc0, 0.f);
     }
@@ -1101,49 +1128,63 @@ __device__ __forceinline__ void tower16_tile(const TowerNet* __restrict__ net, c
   // features, then the 16 partials in order; value Dense(J): P threads per
   // hidden unit, each a strided slice of the pixels for every board, then
   // the P partials in order
+  const int K = 2 * HW, O = nbrd * A, OP = NT / 16;
+  const float* bpd = blob + off_bpd;
+  const float* bv1 = blob + off_bv1;
+  const float* wv2 = blob + off_wv2;
+  const float bv2 = blob[off_hb + 3];
   {
-    const int K = 2 * HW, O = nbrd * A, OP = NT / 16;
-    const float* bpd = blob + T.off_bpd;
-    const float* bv1 = blob + T.off_bv1;
-    const float* wv2 = blob + T.off_wv2;
-    auto policy_part = [&](int base, auto wpd) {
-      const int o = base + tid / 16, pi = tid & 15;
-      float sacc = 0.f;
-      if (o < O) {
-        const int b = o / A, a = o - b * A;
-        const float* pb = pf + b * K;
-        for (int k0 = pi; k0 < K; k0 += 64) {  // 4 features per batch, their reads ahead of the FMAs
-          float xv[4], wv[4];
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const int k = k0 + 16 * u;
-            xv[u] = k < K ? pb[k] : 0.f;
-            wv[u] = k < K ? wpd[k * A + a] : 0.f;
-          }
-#pragma unroll
-          for (int u = 0; u < 4; ++u) sacc = fmaf(xv[u], wv[u], sacc);
-        }
-      }
-      pp[tid] = sacc;
-    };
+    // tid -> (logit of the pass, slice) and (hidden unit, slice), once
+    const int pl = tid >> 4, pi = tid & 15;
+    const int vq = div_small(tid, rJ), vj = tid - vq * J;  // vq: wave-uniform for J >= 64
     // NBV: the boards a pass covers, 4 when the tile holds at most 4 (C4: 3)
     // -- the per-board sums are the same either way, the 8-board form spent
-    // 5/8 of its FMAs on boards the tile does not have
+    // 5/8 of its FMAs on boards the tile does not have.  A batch is 4 pixels,
+    // their reads ahead of their FMAs; whole batches read without the bounds
+    // selects of the last, partial one, and with 4 boards two at a time.  A
+    // board's FMAs -- a partial batch's masked ones included -- are the ones
+    // of single batches, in their order
     auto value_part_n = [&](auto wv1, auto nbv) {
       constexpr int NBV = decltype(nbv)::value;
-      const int j = tid % J, q = tid / J;  // q: wave-uniform for J >= 64
+      const int j = vj, q = vq;
       if (q >= P) return;
       float sv[NBV];
 #pragma unroll
       for (int b = 0; b < NBV; ++b) sv[b] = 0.f;
-      for (int p0 = q; p0 < HW; p0 += 4 * P) {  // 4 pixels per batch, every read ahead of the FMAs
+      const int PJ = P * J;
+      int p0 = q;
+      auto whole = [&](auto nu) {  // NU whole pixels from p0
+        constexpr int NU = decltype(nu)::value;
+        float w[NU], v[NU][NBV];
+        const int iw = p0 * J + j;
+        const float* pv = vf + p0 * kTowerMaxBoards;
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+          w[u] = wv1[iw + u * PJ];
+#pragma unroll
+          for (int h = 0; h < NBV / 4; ++h) {
+            const float4 f = *reinterpret_cast<const float4*>(pv + u * P * kTowerMaxBoards + 4 * h);
+            v[u][4 * h] = f.x, v[u][4 * h + 1] = f.y, v[u][4 * h + 2] = f.z, v[u][4 * h + 3] = f.w;
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < NU; ++u)
+#pragma unroll
+          for (int b = 0; b < NBV; ++b) sv[b] = fmaf(v[u][b], w[u], sv[b]);
+      };
+      if constexpr (NBV == 4) {
+#pragma unroll 1
+        for (; p0 + 7 * P < HW; p0 += 8 * P) whole(IC<8>{});
+      }
+#pragma unroll 1
+      for (; p0 + 3 * P < HW; p0 += 4 * P) whole(IC<4>{});
+      if (p0 < HW) {  // the partial batch: pixels past the board read pixel 0 (past nbrd: stale scratch, never stored) x 0
         float w[4], v[4][NBV];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           const int p = p0 + u * P;
           const int pc = p < HW ? p : 0;
           w[u] = p < HW ? wv1[pc * J + j] : 0.f;
-          // the pixel's boards (past nbrd: stale scratch, never stored)
 #pragma unroll
           for (int h = 0; h < NBV / 4; ++h) {
             const float4 f = *reinterpret_cast<const float4*>(vf + pc * kTowerMaxBoards + 4 * h);
@@ -1159,23 +1200,81 @@ __device__ __forceinline__ void tower16_tile(const TowerNet* __restrict__ net, c
       for (int b = 0; b < NBV; ++b)
         if (b < nbrd) vp[(b * P + q) * J + j] = sv[b];
     };
-    auto value_part = [&](auto wv1) {
-      if (nbrd <= 4) value_part_n(wv1, IC<4>{});
-      else value_part_n(wv1, IC<kTowerMaxBoards>{});
+    auto value_part = [&]() {
+      auto by_boards = [&](auto wv1) {
+        if (nbrd <= 4) value_part_n(wv1, IC<4>{});
+        else value_part_n(wv1, IC<kTowerMaxBoards>{});
+      };
+      // staged with the blob or behind the partials in X's tile: LDS either way, one body
+      if (wv1_lds || wv1_xt) by_boards(wv1_lds ? blob + off_wv1 : reinterpret_cast<const float*>(bufX) + TR * 48);
+      else by_boards(gbl(T.blob + off_wv1));
     };
-    for (int base = 0;; base += OP) {  // block-uniform
-      if (wpd_lds) policy_part(base, blob + T.off_wpd);
-      else policy_part(base, gbl(T.blob + T.off_wpd));
-      if (base == 0) {
-        if (wv1_lds) value_part(blob + T.off_wv1);
-        else if (wv1_xt) value_part(reinterpret_cast<const float*>(bufX) + TR * 48);
-        else value_part(gbl(T.blob + T.off_wv1));
+    // one pass of OP logits.  K <= 128: a thread's whole slice (at most 8
+    // features) is read in one batch, and in the first pass the value dense
+    // runs between those reads and their FMAs (the two are independent: one
+    // round trip for both); the FMAs are the 4-feature batches' in their order
+    auto policy_part = [&](int base) {
+      const int o = base + pl;
+      const bool on = o < O;
+      const int b = div_small(on ? o : 0, rA), a = (on ? o : 0) - b * A;
+      const float* pb = pf + b * K;
+      const bool slice = K <= 128;  // block-uniform
+      float sacc = 0.f, xv[8], wv[8];
+      auto reads = [&](auto wpd) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const int k = pi + 16 * u;
+          const bool in = on && k < K;
+          xv[u] = in ? pb[k] : 0.f;
+          wv[u] = in ? wpd[k * A + a] : 0.f;
+        }
+      };
+      auto batches = [&](auto wpd) {
+        for (int k0 = pi; k0 < K; k0 += 64) {  // 4 features per batch, their reads ahead of the FMAs
+          float x4[4], w4[4];
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            const int k = k0 + 16 * u;
+            x4[u] = k < K ? pb[k] : 0.f;
+            w4[u] = k < K ? wpd[k * A + a] : 0.f;
+          }
+#pragma unroll
+          for (int u = 0; u < 4; ++u) sacc = fmaf(x4[u], w4[u], sacc);
+        }
+      };
+      if (slice) {
+        if (wpd_lds) reads(blob + off_wpd);
+        else reads(gbl(T.blob + off_wpd));
       }
+      if (base == 0) value_part();
+      if (slice) {
+        if (on) {
+#pragma unroll
+          for (int u = 0; u < 4; ++u) sacc = fmaf(xv[u], wv[u], sacc);
+          if (pi + 64 < K) {
+#pragma unroll
+            for (int u = 4; u < 8; ++u) sacc = fmaf(xv[u], wv[u], sacc);
+          }
+        }
+      } else if (on) {
+        if (wpd_lds) batches(blob + off_wpd);
+        else batches(gbl(T.blob + off_wpd));
+      }
+      pp[tid] = sacc;
+    };
+    // one pass holds every logit and the tile at most NT / 128 boards (Connect-4, 9x9 with
+    // gravity): board b's softmax is wave b's and its value wave NT / 128 + b's, each summing
+    // the dense partials of its own outputs in registers -- the sums of the general form
+    // below, without its logits and hidden units in LDS and the barrier that publishes them
+    const bool one_pass = O <= OP && nbrd <= NT / 128;
+    for (int base = 0;; base += OP) {  // block-uniform
+      policy_part(base);
       if (base == 0) T16_STAMP(45);
       __syncthreads();
       if (base == 0) T16_STAMP(46);
+      if (one_pass) break;
       if (tid < OP && base + tid < O) {
-        const int o = base + tid, a = o % A;
+        const int o = base + tid, a = o - div_small(o, rA) * A;
         float t = 0.f;
 #pragma unroll
         for (int j = 0; j < 16; ++j) t += pp[tid * 16 + j];
@@ -1183,7 +1282,7 @@ __device__ __forceinline__ void tower16_tile(const TowerNet* __restrict__ net, c
       }
       if (base == 0) {
         for (int i = tid; i < nbrd * J; i += NT) {
-          const int b = i / J, j = i - b * J;
+          const int b = div_small(i, rJ), j = i - b * J;
           float t = 0.f;
           for (int q = 0; q < P; ++q) t += vp[(b * P + q) * J + j];
           hv[i] = fmaxf(t + bv1[j], 0.f) * wv2[j];
@@ -1193,21 +1292,65 @@ __device__ __forceinline__ void tower16_tile(const TowerNet* __restrict__ net, c
       __syncthreads();
       if (base + OP >= O) break;
     }
-  }
-  // softmax (one wave per board) and tanh
-  const float bv2 = blob[T.off_hb + 3];
-  for (int b = wave; b < nbrd; b += NT / 64) {  // wave-uniform
-    float m = -INFINITY;
-    for (int a = lane; a < A; a += 64) m = fmaxf(m, lg[b * A + a]);
-    m = wmax(m);
-    float z = 0.f;
-    for (int a = lane; a < A; a += 64) z += expf(lg[b * A + a] - m);
-    z = wsum(z);
-    for (int a = lane; a < A; a += 64) probs[(size_t)(b0 + b) * A + a] = expf(lg[b * A + a] - m) / z;
-    float v = 0.f;
-    for (int j = lane; j < J; j += 64) v += hv[b * J + j];
-    v = wsum(v);
-    if (lane == 0) values[b0 + b] = tanhf(v + bv2);
+    if (one_pass) {
+      T16_STAMP(47);
+      if (wave < nbrd) {  // wave-uniform
+        // softmax: lane a's logit from its 16 partials in order; exp(l - m) is evaluated once
+        // (the same expression as the general form's two evaluations: the same bits)
+        const bool on = lane < A;
+        float l = -INFINITY;
+        if (on) {
+          const float* q = pp + (wave * A + lane) * 16;
+          float t = 0.f;
+#pragma unroll
+          for (int j = 0; j < 16; ++j) t += q[j];
+          l = t + bpd[lane];
+        }
+        const float m = wmax(fmaxf(-INFINITY, l));
+        const float e = on ? expf(l - m) : 0.f;
+        const float z = wsum(0.f + e);
+        if (on) probs[(size_t)(b0 + wave) * A + lane] = e / z;
+      } else if (wave >= NT / 128 && wave - NT / 128 < nbrd) {
+        // value: the hidden units lane, lane + 64, ... from their P partials in order.  The
+        // product is rounded before it is added, as when it went through LDS
+#pragma clang fp contract(off)
+        const int b = wave - NT / 128;
+        // (a lane's at most 4 units -- hidden <= 256, tower16_heads_fit -- side by side: each
+        // unit's partials in order, then the units in order)
+        float t[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+        for (int q = 0; q < P; ++q) {
+          const float* pq = vp + (b * P + q) * J + lane;
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+            if (lane + 64 * i < J) t[i] += pq[64 * i];
+        }
+        float v = 0.f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          if (lane + 64 * i < J) {
+            const float h = fmaxf(t[i] + bv1[lane + 64 * i], 0.f) * wv2[lane + 64 * i];
+            v += h;
+          }
+        v = wsum(v);
+        if (lane == 0) values[b0 + b] = tanhf(v + bv2);
+      }
+    } else {
+      // softmax (one wave per board) and tanh
+      for (int b = wave; b < nbrd; b += NT / 64) {  // wave-uniform
+        float m = -INFINITY;
+        for (int a = lane; a < A; a += 64) m = fmaxf(m, lg[b * A + a]);
+        m = wmax(m);
+        float z = 0.f;
+        for (int a = lane; a < A; a += 64) z += expf(lg[b * A + a] - m);
+        z = wsum(z);
+        for (int a = lane; a < A; a += 64) probs[(size_t)(b0 + b) * A + a] = expf(lg[b * A + a] - m) / z;
+        float v = 0.f;
+        for (int j = lane; j < J; j += 64) v += hv[b * J + j];
+        v = wsum(v);
+        if (lane == 0) values[b0 + b] = tanhf(v + bv2);
+      }
+    }
   }
   T16_STAMP(19);
   T16_RSTAMP(23);
