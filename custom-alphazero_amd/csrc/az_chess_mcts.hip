@@ -1272,8 +1272,13 @@ int az_chess_engine_create(int device, const az_chess_config* cfg, az_chess_engi
     return az::fail_abi(AZ_E_INVALID, "unknown evaluator");
   if (c.evaluator == AZ_EVAL_NETWORK && c.filters != 128)
     return az::fail_abi(AZ_E_INVALID, "network evaluator supports filters == 128 (ConfigModel.filters)");
-  if (c.conv_algo != AZ_CONV_F16X2 && c.conv_algo != AZ_CONV_DIRECT && c.conv_algo != AZ_CONV_F16X2_LAYERS)
-    return az::fail_abi(AZ_E_INVALID, "conv_algo must be AZ_CONV_F16X2, AZ_CONV_DIRECT or AZ_CONV_F16X2_LAYERS");
+  if (c.conv_algo != AZ_CONV_F16X2 && c.conv_algo != AZ_CONV_DIRECT && c.conv_algo != AZ_CONV_F16X2_LAYERS &&
+      c.conv_algo != AZ_CONV_F16)
+    return az::fail_abi(AZ_E_INVALID,
+                        "conv_algo must be AZ_CONV_F16X2, AZ_CONV_DIRECT, AZ_CONV_F16X2_LAYERS or AZ_CONV_F16");
+  // the one-term arithmetic exists on the one-launch tower only: no other form stands in for it
+  if (c.conv_algo == AZ_CONV_F16 && (c.depth < 1 || c.depth > az::kTowerMaxDepth))
+    return az::fail_abi(AZ_E_INVALID, "AZ_CONV_F16 needs the one-launch tower: 1 <= depth <= 16");
   if (c.max_plies < 0 || c.arena_edges < 0 || c.depth < 0 || c.value_hidden < 1)
     return az::fail_abi(AZ_E_INVALID, "negative bound");
   if ((int64_t)c.slots * 64 * 512 >= (1ll << 31))
@@ -1367,11 +1372,16 @@ int az_chess_engine_create(int device, const az_chess_config* cfg, az_chess_engi
   e->net.depth = c.depth;
   // depth 0: the fp16x2 chain runs the heads' 1x1 convs inside the last
   // block's conv2, so a tower without blocks takes the fp32 MFMA path
-  e->net.algo = c.depth == 0 ? AZ_CONV_DIRECT : (c.conv_algo == AZ_CONV_F16X2_LAYERS ? AZ_CONV_F16X2 : c.conv_algo);
+  // (AZ_CONV_F16: AZ_CONV_F16X2's packs and input rows, the tower's one-term kernels -- net.terms)
+  e->net.algo = c.depth == 0 ? AZ_CONV_DIRECT
+                             : (c.conv_algo == AZ_CONV_F16X2_LAYERS || c.conv_algo == AZ_CONV_F16 ? AZ_CONV_F16X2
+                                                                                                  : c.conv_algo);
+  e->net.terms = c.conv_algo == AZ_CONV_F16 ? 1 : 3;
   // AZ_CONV_F16X2: the stem, the tower and the heads' 1x1 convs in one launch
   // (tower16_kernel's input-row form) when the network fits it, else the
   // per-layer conv16 chain (AZ_CONV_F16X2_LAYERS forces the chain)
-  e->net.use_tower = c.conv_algo == AZ_CONV_F16X2 && c.depth >= 1 && c.depth <= az::kTowerMaxDepth;
+  e->net.use_tower = (c.conv_algo == AZ_CONV_F16X2 || c.conv_algo == AZ_CONV_F16) && c.depth >= 1 &&
+                     c.depth <= az::kTowerMaxDepth;
   e->net.board_h = e->net.board_w = 8;
   e->net.hidden = c.value_hidden;
   e->net.err = t.stats + az::kStatErrors;
@@ -1496,6 +1506,7 @@ int az_chess_stats(az_chess_engine* e, az_stats* st) {
   if ((rc = az::read_common_stats(st, h, e->t.stats, e->t.game_id, e->g.slots, e->cache)))
     return rc;
   st->issued_flop_per_board = e->net.use_tower && e->net.tower ? e->net.layout.main.issued_flop_per_board : 0.0;
+  if (e->net.terms == 1) st->issued_flop_per_board /= 3;  // AZ_CONV_F16 issues one of the three products
   st->tower_small_max_boards = -1;  // (chess: one tile height)
   std::vector<az::ConvTimer*> timers = {&e->timer};
   for (CLane* L : e->lanes) timers.push_back(&L->timer);

@@ -547,6 +547,8 @@ int load_network(NetDev& net, const az_tensor* tensors, int n, int in_ch, int HW
                                         net.tower_natural_order, net.lanes, cus});
     if (net.layout.ok) {
       AZ_TRY(upload_tower(net, net.layout, f, rows_stem, owned));
+    } else if (net.terms == 1) {
+      return fail(AZ_E_INVALID, "AZ_CONV_F16 needs the one-launch tower, and this network has no layout for it");
     } else {  // the per-layer kernels instead (same arithmetic)
       net.use_tower = false;
       if (net.board_w > 16) net.algo = AZ_CONV_DIRECT;
@@ -580,8 +582,13 @@ int az_engine_create(int device, const az_config* cfg, az_engine** out) {
   const int A = c.gravity ? c.board_width : c.board_width * c.board_height;
   if (A > az::kMaxActions) return fail(AZ_E_INVALID, "action space too large");
   if (c.slots < 1 || c.mcts_iterations < 1) return fail(AZ_E_INVALID, "slots and mcts_iterations must be >= 1");
-  if (c.conv_algo != AZ_CONV_F16X2 && c.conv_algo != AZ_CONV_DIRECT && c.conv_algo != AZ_CONV_F16X2_LAYERS)
-    return fail(AZ_E_INVALID, "conv_algo must be AZ_CONV_F16X2, AZ_CONV_DIRECT or AZ_CONV_F16X2_LAYERS");
+  if (c.conv_algo != AZ_CONV_F16X2 && c.conv_algo != AZ_CONV_DIRECT && c.conv_algo != AZ_CONV_F16X2_LAYERS &&
+      c.conv_algo != AZ_CONV_F16)
+    return fail(AZ_E_INVALID,
+                "conv_algo must be AZ_CONV_F16X2, AZ_CONV_DIRECT, AZ_CONV_F16X2_LAYERS or AZ_CONV_F16");
+  // the one-term arithmetic exists on the one-launch tower only: no other form stands in for it
+  if (c.conv_algo == AZ_CONV_F16 && (c.depth < 1 || c.depth > az::kTowerMaxDepth || c.value_hidden > 256))
+    return fail(AZ_E_INVALID, "AZ_CONV_F16 needs the one-launch tower: 1 <= depth <= 16 and value_hidden <= 256");
   if (c.evaluator == AZ_EVAL_NETWORK && c.conv_algo == AZ_CONV_F16X2_LAYERS && c.board_width > 16)
     return fail(AZ_E_INVALID, "AZ_CONV_F16X2_LAYERS supports boards up to 16 columns");
   if (c.depth < 0 || c.depth > 1024 || c.value_hidden < 1) return fail(AZ_E_INVALID, "need 0 <= depth and value_hidden >= 1");
@@ -718,14 +725,16 @@ int az_engine_create(int device, const az_config* cfg, az_engine** out) {
   e->net.depth = c.depth;
   e->net.board_h = g.H;
   e->net.board_w = g.W;
-  e->net.algo = c.conv_algo == AZ_CONV_F16X2_LAYERS ? AZ_CONV_F16X2 : c.conv_algo;
+  // (AZ_CONV_F16: AZ_CONV_F16X2's packs and input rows, the tower's one-term kernels -- net.terms)
+  e->net.algo = c.conv_algo == AZ_CONV_F16X2_LAYERS || c.conv_algo == AZ_CONV_F16 ? AZ_CONV_F16X2 : c.conv_algo;
+  e->net.terms = c.conv_algo == AZ_CONV_F16 ? 1 : 3;
   // AZ_CONV_F16X2: the one-launch tower when the network fits it (1 <= depth
   // <= 16, value_hidden <= 256, a layout from tower16_choose_layout: load_network),
   // otherwise quietly the same arithmetic per layer -- or, where the per-layer
   // kernels do not apply (depth 0: the heads are fused into the last conv2;
   // boards wider than 16), the fp32 MFMA path; every form within NET_TOL
-  e->net.use_tower = c.conv_algo == AZ_CONV_F16X2 && c.depth >= 1 && c.depth <= az::kTowerMaxDepth &&
-                     c.value_hidden <= 256;
+  e->net.use_tower = (c.conv_algo == AZ_CONV_F16X2 || c.conv_algo == AZ_CONV_F16) && c.depth >= 1 &&
+                     c.depth <= az::kTowerMaxDepth && c.value_hidden <= 256;
   e->net.tower_natural_order = c.tower_natural_order != 0;
   if (c.depth == 0 || (c.conv_algo != AZ_CONV_DIRECT && !e->net.use_tower && c.board_width > 16))
     e->net.algo = AZ_CONV_DIRECT;
@@ -874,8 +883,9 @@ int az_stats_get(az_engine* e, az_stats* st) {
     st->arena_pool_high = (int64_t)h[az::kStatPoolHigh];
   }
   const az::TowerLayout& tl = e->net.layout;  // (all zero, no alt tiles, where the tower is not used)
-  st->issued_flop_per_board = tl.main.issued_flop_per_board;
-  st->issued_flop_per_board_small = tl.alt.issued_flop_per_board;
+  const int per_mac = e->net.terms == 1 ? 3 : 1;  // AZ_CONV_F16 issues one of the three products
+  st->issued_flop_per_board = tl.main.issued_flop_per_board / per_mac;
+  st->issued_flop_per_board_small = tl.alt.issued_flop_per_board / per_mac;
   st->tower_small_max_boards = tl.alt_max_boards;
   return 0;
 }

@@ -63,13 +63,14 @@ void tower16_stem_pack(const double* w, int e, std::vector<uint16_t>& out);
 // L: the layout the TowerNet was filled from (load_network); with alt tiles a dual launch
 void launch_tower16(const TowerNet* net, const TowerLayout& L, const Board* boards, const float4* x, const int* count,
                     int n_max, int H, int W, int A, float* probs, float* values, unsigned long long* err,
-                    hipStream_t s);
+                    hipStream_t s, int terms = 3);
 // the input-row form (chess): rows [n][HW] of 512 B split16 (t0 of F
 // channels, t1 x 2^12; az_nn's store_act4) -> the stem, the residual tower
 // and the heads' 1x1 convs; per pixel float4 (relu(p0), relu(p1), relu(v), 0)
 // into feat [n * HW] for the dense heads' kernels (policy_dense_kernel,
 // heads_tail_kernel).  first_chunk: input channel chunks (32) below it are
-// known zero and skipped (chess self-play: planes 0-63)
+// known zero and skipped (chess self-play: planes 0-63).  terms (both
+// launches): 3, or 1 -- the one-term kernels of AZ_CONV_F16 (NetDev::terms)
 // chess self-play (round 5): the tower builds its boards' input planes in
 // LDS from the leaves the select launch queued -- queue entry b's slot
 // eval_slot[b], its position leaf[slot] (az_chess_pos), path_len / initial
@@ -83,7 +84,7 @@ struct TowerLeaves {
 };
 void launch_tower16_rows(const TowerNet* net, const TowerLayout& L, const void* rows, int first_chunk,
                          const int* count, int n_max, int H, int W, float4* feat, unsigned long long* err,
-                         hipStream_t s, const TowerLeaves* leaves = nullptr);
+                         hipStream_t s, const TowerLeaves* leaves = nullptr, int terms = 3);
 
 // Folded (BatchNorm-in) weights resident in HBM, packed for the kernels (not
 // Keras layouts).  AZ_CONV_F16X2 (default): conv16_kernel packs (fp16 term
@@ -93,6 +94,8 @@ struct NetDev {
   int filters = 128, depth = 0, hidden = 256;
   int algo = 0;             // AZ_CONV_F16X2 / AZ_CONV_DIRECT (one algorithm for every forward)
   bool use_tower = false;   // Connect-N, AZ_CONV_F16X2: the whole forward in tower16_kernel (else per layer)
+  int terms = 3;            // fp16 products per MAC on the tower: 3, or 1 (AZ_CONV_F16: algo stays AZ_CONV_F16X2
+                            // -- the same packs and input rows -- and the launches take the one-term kernels)
   bool tower_natural_order = false;  // az_config.tower_natural_order: no slot plan (A/B, bitwise the same)
   TowerNet* tower = nullptr;  // device copy of the tower's view (load_network)
   TowerLayout layout;         // what it was filled from: tile heights, staging, issued FLOP (az_stats)

@@ -710,7 +710,7 @@ void launch_forward(const NetDev& net, const void* x, const int* count, int n_ma
   if (f16 && net.use_tower && net.in_ch == 4 && net.tower) {  // the whole forward in one launch
     if (timer) timer->begin(s);
     launch_tower16(net.tower, net.layout, boards, boards ? nullptr : static_cast<const float4*>(x), count, n_max, H, W,
-                   A, probs, values, net.err, s);
+                   A, probs, values, net.err, s, net.terms);
     if (timer) timer->end(s, 1);
     return;
   }
@@ -719,7 +719,7 @@ void launch_forward(const NetDev& net, const void* x, const int* count, int n_ma
     // (features into act_a), then the dense heads as below
     if (timer) timer->begin(s);
     launch_tower16_rows(net.tower, net.layout, x, stem_first_chunk, count, n_max, H, W, static_cast<float4*>(act_a),
-                        net.err, s, leaves);
+                        net.err, s, leaves, net.terms);
     if (timer) timer->end(s, 1);
     HeadWeights hw{net.pc_w, net.pc_b, net.vc_w, net.vc_b, net.pd_w,
                    net.pd_b, net.v1_w, net.v1_b, net.v2_w, net.v2_b};

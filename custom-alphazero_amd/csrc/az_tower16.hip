@@ -63,6 +63,7 @@
 #include "az_nn.h"
 #include "az_tree.h"
 #include "az_kloop_asm.h"
+#include "az_kloop_f16_asm.h"
 #include "az_chess.h"
 
 namespace az {
@@ -216,12 +217,19 @@ struct TowerSmem {
 };
 
 // store 4 channels (channel quad cq) of activation row r as split16 terms
+// (TERMS 1, AZ_CONV_F16: the fp16 rounding t0 alone; the row's t1 slots stay unwritten and unread)
+template <int TERMS = 3>
 __device__ __forceinline__ void put4(uint4* act, int r, int cq, const float4 y) {
-  uint2 t0, t1;
-  split_u4(y, t0, t1);
-  char* q = reinterpret_cast<char*>(act) + r * kPitch + cq * 8;
-  *reinterpret_cast<uint2*>(q) = t0;
-  *reinterpret_cast<uint2*>(q + 256) = t1;
+  if constexpr (TERMS == 1) {
+    char* q = reinterpret_cast<char*>(act) + r * kPitch + cq * 8;
+    *reinterpret_cast<uint2*>(q) = make_uint2(pk_f16(y.x, y.y), pk_f16(y.z, y.w));
+  } else {
+    uint2 t0, t1;
+    split_u4(y, t0, t1);
+    char* q = reinterpret_cast<char*>(act) + r * kPitch + cq * 8;
+    *reinterpret_cast<uint2*>(q) = t0;
+    *reinterpret_cast<uint2*>(q + 256) = t1;
+  }
 }
 
 __device__ __forceinline__ float max4(const float4 v) { return fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w)); }
@@ -234,7 +242,7 @@ __device__ __forceinline__ float4 scale4(const float4 v, float s) {
 // their scale.  Returns whether any board of this buffer is scaled (then
 // sc_out holds the exponents).  Contains the barrier that publishes the
 // stores.  `par` alternates per layer (flag[par] is this layer's).
-template <int MBW>
+template <int MBW, int TERMS = 3>
 __device__ __forceinline__ bool store_layer(uint4* act, int HW, int W, const int (&yx_)[MBW], int cq0, const float4 (&y)[2 * MBW],
                                             TowerSmem& sm, int par, int* sc_out, int nbrd,
                                             unsigned long long* err) {
@@ -254,7 +262,7 @@ __device__ __forceinline__ bool store_layer(uint4* act, int HW, int W, const int
   for (int i = 0; i < 2 * MBW; ++i)
     if (row[i / 2] >= 0) {
       vmax = fmaxf(vmax, max4(y[i]));
-      put4(act, row[i / 2], cq0 + 4 * (i & 1), y[i]);
+      put4<TERMS>(act, row[i / 2], cq0 + 4 * (i & 1), y[i]);
     }
   if (!(vmax <= kRange)) sm.flag[par] = 1;  // also NaN
   if (threadIdx.x == 0) sm.flag[par ^ 1] = 0;  // next layer's flag (nobody reads it before then)
@@ -273,7 +281,7 @@ __device__ __forceinline__ bool store_layer(uint4* act, int HW, int W, const int
     const float m = __uint_as_float(sm.bmax[brd[i / 2]]);
     if (!(m <= 3.0e38f)) continue;  // inf/NaN: flagged below, nothing to rescale
     const int s = range_exp(m);
-    if (s) put4(act, row[i / 2], cq0 + 4 * (i & 1), scale4(y[i], ldexpf(1.f, -s)));
+    if (s) put4<TERMS>(act, row[i / 2], cq0 + 4 * (i & 1), scale4(y[i], ldexpf(1.f, -s)));
   }
   if ((int)threadIdx.x < nbrd) {
     const float m = __uint_as_float(sm.bmax[threadIdx.x]);
@@ -519,7 +527,26 @@ __device__ __forceinline__ void k_loop(const uint4* __restrict__ act, const uint
 // steps (may be the same array).  The schedule is checked symbolically by
 // tests/test_kloop_schedule_cpu.py and against the compiled ISA by
 // tests/test_kernel_resources_cpu.py
-template <int MBW, int R, int C0, typename Mid = NoMid>
+//
+// TERMS 1 (AZ_CONV_F16): the one-term groups KGroupH / KProH / KDrainH
+// (gen_kloop_asm.group_asm_h) -- one product t0*B0 per MAC from fragments 0
+// and 2 of the same packs and the t0 half of the same LDS rows, the k-steps
+// in the same order; checked by tests/test_kloop_f16_schedule_cpu.py and
+// tests/test_kernel_resources_f16_cpu.py
+template <int TERMS, int MBW, int C0, int SKC, int PF>
+struct KG : KGroup<MBW, C0, SKC, PF, AZ_KLOOP_TERM> {};
+template <int MBW, int C0, int SKC, int PF>
+struct KG<1, MBW, C0, SKC, PF> : KGroupH<MBW, C0, SKC, PF> {};
+template <int TERMS, int MBW, int C0, int PF>
+struct KP : KPro<MBW, C0, PF, AZ_KLOOP_TERM> {};
+template <int MBW, int C0, int PF>
+struct KP<1, MBW, C0, PF> : KProH<MBW, C0, PF> {};
+template <int TERMS, int MBW, int NB>
+struct KD : KDrain<MBW, NB> {};
+template <int MBW, int NB>
+struct KD<1, MBW, NB> : KDrainH<MBW, NB> {};
+
+template <int MBW, int R, int C0, typename Mid = NoMid, int TERMS = 3>
 __device__ __forceinline__ void k_loop_asm(const uint4* __restrict__ act, const uint4* __restrict__ wmain,
                                            const uint4* __restrict__ wres, t_f4 (&accm)[MBW][2],
                                            t_f4 (&accr)[MBW][2], const int (&yx_)[MBW], int H, int W,
@@ -565,13 +592,14 @@ __device__ __forceinline__ void k_loop_asm(const uint4* __restrict__ act, const 
   // 8 buffers picked by the tap's parity -- gen_kloop_asm.nbufs -- spilled
   // 627 VGPRs in chess's 2-block waves, one body per parity)
   constexpr int PF = C0 == 0 && MBW < 6 ? AZ_KLOOP_PF : 1, NB = PF == 1 ? 2 : 4;
-  az_u4 aq[MBW][2], bq[NB][4];
+  std::conditional_t<TERMS == 1, az_u4[MBW], az_u4[MBW][2]> aq;
+  std::conditional_t<TERMS == 1, az_u4[NB][2], az_u4[NB][4]> bq;
   int cur[MBW], nxt[MBW];
   // prologue (asm too: a compiler load here would leave the compiler waiting
   // for it, vmcnt(0) lgkmcnt(0), before every group of the loop)
   if (R) own(cur);
   else tap_addr(0, cur);
-  KPro<MBW, C0, PF, AZ_KLOOP_TERM>::run(aq, bq, cur, voff, R ? rs_r : rs_m, R ? 36 * 16384 : C0 * 16384);
+  KP<TERMS, MBW, C0, PF>::run(aq, bq, cur, voff, R ? rs_r : rs_m, R ? 36 * 16384 : C0 * 16384);
   const bool young = __builtin_amdgcn_readfirstlane((int)threadIdx.x) >= 256;
   auto prio = [&](bool hi) {
     if (hi) __builtin_amdgcn_s_setprio(1);
@@ -580,7 +608,7 @@ __device__ __forceinline__ void k_loop_asm(const uint4* __restrict__ act, const 
   prio(young);
   if constexpr (R) {
     tap_addr(0, nxt);
-    KGroup<MBW, 0, 0, PF, AZ_KLOOP_TERM>::run(accr, aq, bq, cur, nxt, voff, rs_r, rs_m, 36 * 16384, 0);
+    KG<TERMS, MBW, 0, 0, PF>::run(accr, aq, bq, cur, nxt, voff, rs_r, rs_m, 36 * 16384, 0);
 #pragma unroll
     for (int mb = 0; mb < MBW; ++mb) cur[mb] = nxt[mb];
     mid();
@@ -589,7 +617,6 @@ __device__ __forceinline__ void k_loop_asm(const uint4* __restrict__ act, const 
   // the last tap's prefetch re-reads its own first k-steps (drained; a peeled
   // last tap without them -- the generator's HASNEXT = 0 groups -- made the
   // allocator spill 400-550 VGPRs in the 128-row kernels)
-  constexpr int O = AZ_KLOOP_TERM;
 #pragma unroll 1
   for (int t = 0; t < 9; ++t) {
     if (t == 6) prio(!young);
@@ -600,13 +627,13 @@ __device__ __forceinline__ void k_loop_asm(const uint4* __restrict__ act, const 
     }
     const int m = (skw >> (2 * t)) & 3;
     const int sc = 4 * t * 16384, sn = t < 8 ? (4 * (t + 1) + C0) * 16384 : sc + C0 * 16384;
-    if (m == 0) KGroup<MBW, C0, 0, PF, O>::run(accm, aq, bq, cur, nxt, voff, rs_m, rs_m, sc, sn);
-    else if (m == 1) KGroup<MBW, C0, (MBW > 1 ? 1 : 0), PF, O>::run(accm, aq, bq, cur, nxt, voff, rs_m, rs_m, sc, sn);
-    else KGroup<MBW, C0, (MBW > 1 ? 2 : 0), PF, O>::run(accm, aq, bq, cur, nxt, voff, rs_m, rs_m, sc, sn);
+    if (m == 0) KG<TERMS, MBW, C0, 0, PF>::run(accm, aq, bq, cur, nxt, voff, rs_m, rs_m, sc, sn);
+    else if (m == 1) KG<TERMS, MBW, C0, (MBW > 1 ? 1 : 0), PF>::run(accm, aq, bq, cur, nxt, voff, rs_m, rs_m, sc, sn);
+    else KG<TERMS, MBW, C0, (MBW > 1 ? 2 : 0), PF>::run(accm, aq, bq, cur, nxt, voff, rs_m, rs_m, sc, sn);
 #pragma unroll
     for (int mb = 0; mb < MBW; ++mb) cur[mb] = nxt[mb];
   }
-  KDrain<MBW, NB>::run(accm, aq, bq);
+  KD<TERMS, MBW, NB>::run(accm, aq, bq);
   __builtin_amdgcn_s_setprio(0);
 }
 
@@ -618,6 +645,17 @@ __device__ __forceinline__ void k_loop_asm(const uint4* __restrict__ act, const 
 #else
 #define AZ_KLOOP k_loop_asm
 #endif
+// the K loop by its number of terms: 3 -- AZ_KLOOP; 1 -- the one-term assembly groups
+template <int TERMS, int MBW, int R, int C0, typename Mid = NoMid>
+__device__ __forceinline__ void k_loop_t(const uint4* __restrict__ act, const uint4* __restrict__ wmain,
+                                         const uint4* __restrict__ wres, t_f4 (&accm)[MBW][2], t_f4 (&accr)[MBW][2],
+                                         const int (&yx)[MBW], int H, int W, int zrow, int nq, int lane, int skw,
+                                         int res_shift = 0, Mid mid = Mid{}) {
+  if constexpr (TERMS == 1)
+    k_loop_asm<MBW, R, C0, Mid, 1>(act, wmain, wres, accm, accr, yx, H, W, zrow, nq, lane, skw, res_shift, mid);
+  else
+    AZ_KLOOP<MBW, R, C0, Mid>(act, wmain, wres, accm, accr, yx, H, W, zrow, nq, lane, skw, res_shift, mid);
+}
 
 // LDS-DMA of n_u4 16-byte words from global src into LDS dst (both
 // 16-byte aligned), the workgroup's waves in turn: no VGPRs, completes in the
@@ -639,8 +677,10 @@ __device__ __forceinline__ void dma_to_lds(uint4* dst, const float* src, int n_u
 // (chess, launch_tower16_rows): the stem is a 3x3 conv over F (padded) input
 // channels read from split16 rows, and the kernel ends with the heads' 1x1
 // convs (per pixel float4 features into feat) -- the dense heads (1880
-// logits) run in their own kernels
-template <int MBT, int NWM, bool ROWS, bool DB>
+// logits) run in their own kernels.  TERMS: fp16 products per MAC -- 3
+// (t1*B0 + t0*b1 + t0*B0, fp32-accurate) or 1 (AZ_CONV_F16: t0*B0; a stored
+// activation is its fp16 rounding t0, the rows' t1 slots are not touched)
+template <int MBT, int NWM, bool ROWS, bool DB, int TERMS = 3>
 __device__ __forceinline__ void tower16_tile(const TowerNet* __restrict__ net, const Board* __restrict__ boards,
                                              const float4* __restrict__ x, const uint4* __restrict__ rows,
                                              int n, int H, int W, int A, int bpw, float* __restrict__ probs,
@@ -757,10 +797,16 @@ __device__ __forceinline__ void tower16_tile(const TowerNet* __restrict__ net, c
         split16x4(make_float4(v[0], v[1], v[2], v[3]), t0, t1);
         char* q = dst + rr * kPitch;
         *reinterpret_cast<uint2*>(q + 8 * c4) = t0;
-        *reinterpret_cast<uint2*>(q + 256 + 8 * c4) = make_uint2(t1_unscale(t1.x), t1_unscale(t1.y));
+        if constexpr (TERMS != 1)
+          *reinterpret_cast<uint2*>(q + 256 + 8 * c4) = make_uint2(t1_unscale(t1.x), t1_unscale(t1.y));
       }
     } else {
       const uint4* src = rows + (size_t)b0 * HW * 32;
+      if constexpr (TERMS == 1) {  // the rows' t0 halves only
+#pragma unroll 4
+        for (int i = tid; i < live * 16; i += NT)
+          *reinterpret_cast<uint4*>(dst + (i >> 4) * kPitch + (i & 15) * 16) = gld(src + (i >> 4) * 32 + (i & 15));
+      } else
 #pragma unroll 4
       for (int i = tid; i < live * 32; i += NT) {
         uint4 v = gld(src + i);
@@ -774,8 +820,8 @@ __device__ __forceinline__ void tower16_tile(const TowerNet* __restrict__ net, c
       for (int nb = 0; nb < 2; ++nb) acc[mb][nb] = t_f4{0.f, 0.f, 0.f, 0.f};
     __builtin_amdgcn_s_waitcnt(0);  // this wave's blob DMA pieces have landed ...
     __syncthreads();                // ... every wave's, and the input rows
-    if (first_chunk == 2) AZ_KLOOP<MBW, 0, 2>(bufH, T.stem_k, nullptr, acc, acc, yx, H, W, zH, nq, lane, skw);
-    else AZ_KLOOP<MBW, 0, 0>(bufH, T.stem_k, nullptr, acc, acc, yx, H, W, zH, nq, lane, skw);
+    if (first_chunk == 2) k_loop_t<TERMS, MBW, 0, 2>(bufH, T.stem_k, nullptr, acc, acc, yx, H, W, zH, nq, lane, skw);
+    else k_loop_t<TERMS, MBW, 0, 0>(bufH, T.stem_k, nullptr, acc, acc, yx, H, W, zH, nq, lane, skw);
     if (!dbuf) __syncthreads();  // in place: every wave is done reading the input before X overwrites it
   } else {
   // conv3x3 4 -> F + folded BN + ReLU on the MFMA: k = tap*4 + plane (36 of
@@ -856,8 +902,10 @@ __device__ __forceinline__ void tower16_tile(const TowerNet* __restrict__ net, c
           // t1*B0 + t0*b1 + t0*B0 per N block, as the K loop's k-step
 #pragma unroll
           for (int nb = 0; nb < 2; ++nb) {
+            if constexpr (TERMS != 1) {
             acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(B0[nb], __builtin_bit_cast(t_h8, a1), acc[mb][nb], 0, 0, 0);
             acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(B1[nb], __builtin_bit_cast(t_h8, a0), acc[mb][nb], 0, 0, 0);
+            }
             acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(B0[nb], __builtin_bit_cast(t_h8, a0), acc[mb][nb], 0, 0, 0);
           }
         }
@@ -886,7 +934,7 @@ __device__ __forceinline__ void tower16_tile(const TowerNet* __restrict__ net, c
   }
   int par = 0;
   // scale state: buffer contents X (block input) and H (conv1 output)
-  bool anyX = store_layer<MBW>(bufX, HW, W, yx, cq0, yv, sm, par, sm.sc[0], nbrd, err);
+  bool anyX = store_layer<MBW, TERMS>(bufX, HW, W, yx, cq0, yv, sm, par, sm.sc[0], nbrd, err);
   bool anyH = false;
   float* red = nullptr;  // the heads' 1x1 partials [TR][16][3] (set by the last block)
   const int J = T.hidden;  // value head hidden units
@@ -909,8 +957,8 @@ __device__ __forceinline__ void tower16_tile(const TowerNet* __restrict__ net, c
       }
     // conv1, input X (in place: + the projection residual into accr)
     T16_WSTAMP(d, 0);
-    if constexpr (DB) AZ_KLOOP<MBW, 0, 0>(bufX, T.k1[d], nullptr, acc, acc, yx, H, W, zX, nq, lane, skw);
-    else AZ_KLOOP<MBW, 4, 0>(bufX, T.k1[d], T.k2[d], acc, accr_, yx, H, W, zX, nq, lane, skw);
+    if constexpr (DB) k_loop_t<TERMS, MBW, 0, 0>(bufX, T.k1[d], nullptr, acc, acc, yx, H, W, zX, nq, lane, skw);
+    else k_loop_t<TERMS, MBW, 4, 0>(bufX, T.k1[d], T.k2[d], acc, accr_, yx, H, W, zX, nq, lane, skw);
     T16_WSTAMP(d, 1);
     if (d < 4) T16_STAMP(2 + 4 * d);
     if (d < 4) T16_STAMP4(24 + 4 * d);
@@ -931,7 +979,7 @@ __device__ __forceinline__ void tower16_tile(const TowerNet* __restrict__ net, c
         }
       }
     }
-    anyH = store_layer<MBW>(bufH, HW, W, yx, cq0, yv, sm, par, sm.sc[1], nbrd, err);
+    anyH = store_layer<MBW, TERMS>(bufH, HW, W, yx, cq0, yv, sm, par, sm.sc[1], nbrd, err);
     par ^= 1;
     if (d < 4) T16_STAMP(3 + 4 * d);
     // the residual was accumulated at X's scale, conv2 runs at H's
@@ -970,12 +1018,12 @@ __device__ __forceinline__ void tower16_tile(const TowerNet* __restrict__ net, c
       for (int mb = 0; mb < MBW; ++mb)
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb) acc[mb][nb] = t_f4{0.f, 0.f, 0.f, 0.f};  // conv1's sums are stored
-      AZ_KLOOP<MBW, 4, 0>(bufH, T.k2[d], T.k2[d], acc, acc, yx, H, W, zH, nq, lane, skw, -(TR + kZeroRows),
+      k_loop_t<TERMS, MBW, 4, 0>(bufH, T.k2[d], T.k2[d], acc, acc, yx, H, W, zH, nq, lane, skw, -(TR + kZeroRows),
                             mid);
     } else {
       rescale();
       // conv2 on H, on top of the residual
-      AZ_KLOOP<MBW, 0, 0>(bufH, T.k2[d], nullptr, accr, accr, yx, H, W, zH, nq, lane, skw);
+      k_loop_t<TERMS, MBW, 0, 0>(bufH, T.k2[d], nullptr, accr, accr, yx, H, W, zH, nq, lane, skw);
     }
     T16_WSTAMP(d, 3);
     if (d < 4) T16_STAMP(4 + 4 * d);
@@ -994,7 +1042,7 @@ __device__ __forceinline__ void tower16_tile(const TowerNet* __restrict__ net, c
                                         fmaxf(fmaf(a[2], o, bc.z), 0.f), fmaxf(fmaf(a[3], o, bc.w), 0.f));
         }
       }
-      anyX = store_layer<MBW>(bufX, HW, W, yx, cq0, yv, sm, par, sm.sc[0], nbrd, err);
+      anyX = store_layer<MBW, TERMS>(bufX, HW, W, yx, cq0, yv, sm, par, sm.sc[0], nbrd, err);
       par ^= 1;
       if (d < 4) T16_STAMP(5 + 4 * d);
       continue;
@@ -1401,6 +1449,38 @@ __global__ __launch_bounds__(512, 2) void tower16_dual_kernel(const TowerNet* __
     tower16_tile<MBT, 2, false, DB>(net, boards, x, nullptr, n, H, W, A, bpw, probs, values, nullptr, 0, err, {});
 }
 
+// The one-term kernels (AZ_CONV_F16): the same tiles at TERMS = 1, under
+// names of their own (tests/test_kernel_resources_f16_cpu.py)
+template <int MBT, int NWM, bool ROWS, bool DB>
+__global__ __launch_bounds__(NWM * 256, NWM) void tower16h_kernel(const TowerNet* __restrict__ net,
+                                                                const Board* __restrict__ boards,
+                                                                const float4* __restrict__ x,
+                                                                const uint4* __restrict__ rows,
+                                                                const int* __restrict__ count, int n_static,
+                                                                int H, int W, int A, int bpw,
+                                                                float* __restrict__ probs,
+                                                                float* __restrict__ values,
+                                                                float4* __restrict__ feat, int first_chunk,
+                                                                unsigned long long* __restrict__ err,
+                                                                TowerLeaves lv) {
+  tower16_tile<MBT, NWM, ROWS, DB, 1>(net, boards, x, rows, count ? *count : n_static, H, W, A, bpw, probs, values,
+                                      feat, first_chunk, err, lv);
+}
+template <int MBT, int MBT2, bool DB>
+__global__ __launch_bounds__(512, 2) void tower16h_dual_kernel(const TowerNet* __restrict__ net,
+                                                               const Board* __restrict__ boards,
+                                                               const float4* __restrict__ x,
+                                                               const int* __restrict__ count, int n_static,
+                                                               int H, int W, int A, int bpw, int bpw2,
+                                                               float* __restrict__ probs, float* __restrict__ values,
+                                                               unsigned long long* __restrict__ err) {
+  const int n = count ? *count : n_static;
+  if (n <= net->alt_max_boards)  // uniform over the launch
+    tower16_tile<MBT2, 2, false, DB, 1>(net, boards, x, nullptr, n, H, W, A, bpw2, probs, values, nullptr, 0, err, {});
+  else
+    tower16_tile<MBT, 2, false, DB, 1>(net, boards, x, nullptr, n, H, W, A, bpw, probs, values, nullptr, 0, err, {});
+}
+
 }  // namespace
 
 #ifdef AZ_T16_STAMPS
@@ -1710,22 +1790,27 @@ struct TowerLaunch {
   unsigned long long* err;
   hipStream_t s;
   TowerLeaves lv;
+  int terms;  // 3, or 1: the one-term kernels (AZ_CONV_F16)
 };
 
-template <int MBT, int NWM, bool ROWS, bool DB>
-static void launch_db(const TowerLaunch& a) {
+template <int MBT, int NWM, bool ROWS, bool DB, int TERMS>
+static void launch_terms(const TowerLaunch& a) {
   const int bpw = tower16_boards_per_tile(a.H * a.W, 16 * MBT);
   const int grid = (a.n_max + bpw - 1) / bpw;
   const size_t bytes = tower16_lds_bytes(a.H * a.W, 16 * MBT, a.staged, DB);
+  constexpr auto kernel = TERMS == 1 ? &tower16h_kernel<MBT, NWM, ROWS, DB> : &tower16_kernel<MBT, NWM, ROWS, DB>;
   static bool attr = false;
   if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tower16_kernel<MBT, NWM, ROWS, DB>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTowerLdsMax);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)kTowerLdsMax);
     attr = true;
   }
-  tower16_kernel<MBT, NWM, ROWS, DB><<<grid, NWM * 256, bytes, a.s>>>(a.net, a.boards, a.x, a.rows, a.count, a.n_max,
-                                                                      a.H, a.W, a.A, bpw, a.probs, a.values, a.feat,
-                                                                      a.first_chunk, a.err, a.lv);
+  kernel<<<grid, NWM * 256, bytes, a.s>>>(a.net, a.boards, a.x, a.rows, a.count, a.n_max, a.H, a.W, a.A, bpw, a.probs,
+                                          a.values, a.feat, a.first_chunk, a.err, a.lv);
+}
+template <int MBT, int NWM, bool ROWS, bool DB>
+static void launch_db(const TowerLaunch& a) {
+  a.terms == 1 ? launch_terms<MBT, NWM, ROWS, DB, 1>(a) : launch_terms<MBT, NWM, ROWS, DB, 3>(a);
 }
 template <int MBT, int NWM, bool ROWS>
 static void launch_mbw(const TowerLaunch& a) {
@@ -1734,7 +1819,7 @@ static void launch_mbw(const TowerLaunch& a) {
 
 void launch_tower16(const TowerNet* net, const TowerLayout& L, const Board* boards, const float4* x, const int* count,
                     int n_max, int H, int W, int A, float* probs, float* values, unsigned long long* err,
-                    hipStream_t s) {
+                    hipStream_t s, int terms) {
   if (n_max <= 0) return;
   if (L.alt.rows) {  // Connect-4 (128-row tiles double-buffered, 96-row alt): either height by the live count
     const int bpw = tower16_boards_per_tile(H * W, 128), bpw2 = tower16_boards_per_tile(H * W, 96);
@@ -1745,14 +1830,20 @@ void launch_tower16(const TowerNet* net, const TowerLayout& L, const Board* boar
     if (!attr) {
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tower16_dual_kernel<8, 6, true>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTowerLdsMax);
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tower16h_dual_kernel<8, 6, true>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTowerLdsMax);
       attr = true;
     }
+    if (terms == 1)
+      tower16h_dual_kernel<8, 6, true><<<grid, 512, bytes, s>>>(net, boards, x, count, n_max, H, W, A, bpw, bpw2, probs,
+                                                                values, err);
+    else
     tower16_dual_kernel<8, 6, true><<<grid, 512, bytes, s>>>(net, boards, x, count, n_max, H, W, A, bpw, bpw2, probs,
                                                              values, err);
     return;
   }
   const TowerLaunch a{net, L.main.staged_floats, L.dbuf, boards, x, nullptr, count, n_max, H, W, A, probs, values,
-                      nullptr, 0, err, s, {}};
+                      nullptr, 0, err, s, {}, terms};
   if (L.main.rows == 192)  // in place only (two 192-row tiles exceed the LDS)
     launch_db<12, 2, false, false>(a);
   else if (L.main.rows == 96)
@@ -1763,12 +1854,12 @@ void launch_tower16(const TowerNet* net, const TowerLayout& L, const Board* boar
 
 void launch_tower16_rows(const TowerNet* net, const TowerLayout& L, const void* rows, int first_chunk,
                          const int* count, int n_max, int H, int W, float4* feat, unsigned long long* err,
-                         hipStream_t s, const TowerLeaves* leaves) {
+                         hipStream_t s, const TowerLeaves* leaves, int terms) {
   if (n_max <= 0 || L.main.rows != 128) return;
   // the leaves' planes are built for the self-play stem (planes 64-127)
   const TowerLeaves lv = leaves && first_chunk == 2 ? *leaves : TowerLeaves{};
   const TowerLaunch a{net, L.main.staged_floats, L.dbuf, nullptr, nullptr, static_cast<const uint4*>(rows), count,
-                      n_max, H, W, 0, nullptr, nullptr, feat, first_chunk == 2 ? 2 : 0, err, s, lv};
+                      n_max, H, W, 0, nullptr, nullptr, feat, first_chunk == 2 ? 2 : 0, err, s, lv, terms};
   // a launch of fewer than 512 boards (chess self-play: 128 per lane) in
   // 2-board tiles would hold under a quarter of the 256 CUs: one board per
   // 64-row tile then (MI355X has 256 CUs; the same sums, bitwise), 8 waves of

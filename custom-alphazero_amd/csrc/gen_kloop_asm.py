@@ -31,11 +31,17 @@ Schedule per k-step (chunk c of a tap; the LAG ring of az_tower16.hip):
     leaves no MFMA in between);
   * s_waitcnt vmcnt / lgkmcnt counted from the issue order (reads of the
     previous group's tail included).
-Run: python gen_kloop_asm.py  (writes az_kloop_asm.h beside it)
+The one-term loop of AZ_CONV_F16 (one product t0*B0 per MAC) has emitters
+of its own -- group_asm_h, prologue_asm_h, emit_h: KGroupH / KProH / KDrainH
+-- written to a header of their own, az_kloop_f16_asm.h (it includes
+az_kloop_asm.h for the operand types); az_kloop_asm.h stays byte for byte
+what it was.
+Run: python gen_kloop_asm.py  (writes both headers beside it)
 """
 import os
 
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "az_kloop_asm.h")
+OUT_H = os.path.join(os.path.dirname(os.path.abspath(__file__)), "az_kloop_f16_asm.h")  # the one-term groups
 KSTEP = 16384  # bytes of one k-step's packed B fragments (az_tower16.hip load_bk)
 
 
@@ -297,6 +303,193 @@ def prologue_asm(MBW, C0, PF, TP=0):
     return "\\n\\t".join(text)
 
 
+WAR_GAP = 2  # group_asm_h's rule: MFMAs between a register's last reader and a load into it
+
+
+def group_asm_h(MBW, C0, SKC, PF=1, HASNEXT=1, TP=0):
+    """One group of the one-term loop (AZ_CONV_F16: one product t0*B0 per
+    MAC): block-major like group_asm, per k-step and unskipped block the pair
+    c_0 += B0[n block 0] * t0, c_1 += B0[n block 1] * t0.  Only fragments 0
+    and 2 of a k-step's pack are loaded (2 buffer loads, into bq[.][0..1],
+    operands %[bJ_0] %[bJ_2]) and only the term-0 half of an LDS row is read
+    (one ds_read_b128 per block, operands %[aK_0]); the other operands are
+    group_asm's.  The ring reads sit where group_asm's do (after block 0 the
+    last block's fragment of this chunk, after block mb >= 1 block mb-1's of
+    the next chunk or the next group); the weights of the k-step PF ahead go
+    out at the k-step's start (PF >= 2: their buffer's last reader is two
+    k-steps back) or after its first pair (PF = 1: the buffer is the previous
+    k-step's).
+
+    WAR rule (the three-term schedules' distance of 6 MFMAs does not exist
+    here: a block has 2): between the last MFMA that reads a register and a
+    ds_read / buffer_load that targets it lie at least WAR_GAP = 2 other
+    MFMAs -- the distance term_group_asm keeps for its t0 reads -- or an
+    `s_nop 4`.  The emitter counts the distance for every load it issues and
+    puts the nop where it is short (a skipped block); a group ends with the
+    seam's two `s_nop 7`, so every register is free at the next group's
+    entry.  tests/test_kloop_f16_schedule_cpu.py checks the rule.
+
+    Waits are exact: the emitter keeps both counters' queues (in flight at
+    entry: the first PF k-steps' fragment pairs; blocks 0..MBW-2 of chunk C0)
+    and waits for a register with the number of loads issued after its own."""
+    assert MBW >= 2, "a one-block wave would read its slot right behind its own pair"
+    lines = []
+    emit = lines.append
+    NB = nbufs(PF)
+    skipped = lambda mb: (SKC >> mb) & 1  # noqa: E731
+    vm = [f"b{(4 * TP + C0 + k) % NB}_{q}" for k in range(PF) for q in (0, 2)]
+    lg = [f"a{b}_0" for b in range(MBW - 1)]
+    state = {"mf": 0}
+    reader = {}  # register -> MFMAs issued when its last reader went out
+
+    def wait(queue, reg, counter, cap):
+        if reg in queue:
+            i = len(queue) - 1 - queue[::-1].index(reg)
+            emit(f"s_waitcnt {counter}({min(len(queue) - 1 - i, cap)})")
+            del queue[:i + 1]
+
+    def load(queue, reg, text):
+        if reg in reader and state["mf"] - reader[reg] < WAR_GAP:
+            emit("s_nop 4")
+            reader.clear()
+        assert reg not in queue, reg
+        emit(text)
+        queue.append(reg)
+
+    def mfma(acc, b, a):
+        emit(f"v_mfma_f32_16x16x32_f16 %[{acc}], %[{b}], %[{a}], %[{acc}]")
+        state["mf"] += 1
+        reader[b] = reader[a] = state["mf"]
+
+    for c in range(C0, 4):
+        last_chunk = c == 3
+        bs = (4 * TP + c) % NB
+        k = c + PF
+        emit(f"; k-step chunk {c}")
+
+        def prefetch():
+            bn = (4 * TP + (k if k < 4 else C0 + k)) % NB
+            if k < 4:
+                emit(f"s_add_u32 %[tmp], %[sc], {k * KSTEP}")
+                src = "%[rc], %[tmp]"
+            elif k == 4:
+                src = "%[rn], %[sn]"
+            else:
+                emit(f"s_add_u32 %[tmp], %[sn], {(k - 4) * KSTEP}")
+                src = "%[rn], %[tmp]"
+            for q in (0, 2):
+                load(vm, f"b{bn}_{q}", f"buffer_load_dwordx4 %[b{bn}_{q}], %[voff], {src} offen offset:{q * 1024}")
+
+        todo = k < 4 or HASNEXT
+        if todo and PF > 1:
+            prefetch()
+            todo = False
+        for mb in range(MBW):
+            if not skipped(mb):
+                wait(lg, f"a{mb}_0", "lgkmcnt", 15)
+                wait(vm, f"b{bs}_0", "vmcnt", 63)
+                mfma(f"c{mb}_0", f"b{bs}_0", f"a{mb}_0")
+                wait(vm, f"b{bs}_2", "vmcnt", 63)
+                mfma(f"c{mb}_1", f"b{bs}_2", f"a{mb}_0")
+                if todo:
+                    prefetch()
+                    todo = False
+            rd = None
+            if mb == 0:
+                if not skipped(MBW - 1):
+                    rd = (MBW - 1, c, f"%[d{MBW - 1}]")
+            elif not last_chunk:
+                if not skipped(mb - 1):
+                    rd = (mb - 1, c + 1, f"%[d{mb - 1}]")
+            elif HASNEXT:
+                rd = (mb - 1, C0, f"%[n{mb - 1}]")
+            if rd is not None:
+                blk, ch, addr = rd
+                load(lg, f"a{blk}_0", f"ds_read_b128 %[a{blk}_0], {addr} offset:{64 * ch}")
+        # a k-step without MFMAs (no slot plan has one): its buffer still lands before it is reused
+        wait(vm, f"b{bs}_2", "vmcnt", 63)
+        if todo:
+            prefetch()
+    emit("s_nop 7")
+    emit("s_nop 7")
+    return "\\n\\t".join(lines)
+
+
+def prologue_asm_h(MBW, C0, PF, TP=0):
+    """group_asm_h's entry state: the first PF k-steps' fragments 0 and 2,
+    then the t0 fragments of blocks 0..MBW-2 at chunk C0."""
+    NB = nbufs(PF)
+    text = []
+    for k in range(PF):
+        if k:
+            text.append(f"s_add_u32 %[tmp], %[sc], {k * KSTEP}")
+        for q in (0, 2):
+            text.append(f"buffer_load_dwordx4 %[b{(4 * TP + C0 + k) % NB}_{q}], %[voff], %[rc], "
+                        f"{'%[tmp]' if k else '%[sc]'} offen offset:{q * 1024}")
+    for blk in range(MBW - 1):
+        text.append(f"ds_read_b128 %[a{blk}_0], %[d{blk}] offset:{64 * C0}")
+    return "\\n\\t".join(text)
+
+
+# the one-term kernels' forms, blocks per wave -> (C0, PF): 64-, 96-, 128- and 192-row tiles at
+# k_loop_asm's prefetch depths; C0 = 2 is the input-row stem of chess self-play (128 and 64 rows)
+H_FORMS = {2: ((0, 2), (2, 1)), 3: ((0, 2),), 4: ((0, 2), (2, 1)), 6: ((0, 1),)}
+
+
+def emit_h(out):
+    """The one-term structs KGroupH / KProH / KDrainH (az_kloop_f16_asm.h)."""
+    out.append("// ---- one-term groups (AZ_CONV_F16; group_asm_h): aq[MBW] holds t0 only, bq[NB][2] fragments 0 and 2\n"
+               "template <int MBW, int C0, int SKC, int PF, int HN = 1, int TP = 0>\nstruct KGroupH;\n"
+               "template <int MBW, int C0, int PF, int TP = 0>\nstruct KProH;\n"
+               "template <int MBW, int NB>\nstruct KDrainH;\n")
+    count = 0
+    for MBW, forms in H_FORMS.items():
+        for C0, PF in forms:
+            NB = nbufs(PF)
+            a_ops = [f'[a{k}_0] "+v"(aq[{k}])' for k in range(MBW)]
+            b_ops = [f'[b{j}_{2 * q}] "+v"(bq[{j}][{q}])' for j in range(NB) for q in range(2)]
+            outs = a_ops + b_ops + ['[tmp] "=&s"(tmp)']
+            ins = [f'[d{k}] "v"(ad[{k}])' for k in range(MBW)] + ['[voff] "v"(voff)', '[rc] "s"(rc)', '[sc] "s"(sc)']
+            out.append(f"template <>\nstruct KProH<{MBW}, {C0}, {PF}, 0> {{\n"
+                       f"  __device__ __forceinline__ static void run(az_u4 (&aq)[{MBW}], az_u4 (&bq)[{NB}][2],\n"
+                       f"      const int (&ad)[{MBW}], int voff, az_rsrc rc, int sc) {{\n"
+                       f"    int tmp;\n"
+                       f"    asm volatile(\"{prologue_asm_h(MBW, C0, PF)}\"\n"
+                       f"        : {', '.join(outs)}\n"
+                       f"        : {', '.join(ins)}\n"
+                       f"        : \"memory\");\n"
+                       f"  }}\n}};\n")
+            outs += [f'[c{k}_{n}] "+v"(acc[{k}][{n}])' for k in range(MBW) for n in range(2)]
+            ins = [f'[d{k}] "v"(ad[{k}])' for k in range(MBW)] + [f'[n{k}] "v"(an[{k}])' for k in range(MBW)]
+            ins += ['[voff] "v"(voff)', '[rc] "s"(rc)', '[rn] "s"(rn)', '[sc] "s"(sc)', '[sn] "s"(sn)']
+            for SKC in (0, 1, 2):
+                for HN in (1,):  # k_loop_asm's last tap prefetches its own first k-steps again (HN = 0 unused)
+                    count += 1
+                    out.append(f"template <>\nstruct KGroupH<{MBW}, {C0}, {SKC}, {PF}, {HN}, 0> {{\n"
+                               f"  __device__ __forceinline__ static void run(az_f4 (&acc)[{MBW}][2], az_u4 (&aq)[{MBW}], az_u4 (&bq)[{NB}][2],\n"
+                               f"      const int (&ad)[{MBW}], const int (&an)[{MBW}], int voff, az_rsrc rc, az_rsrc rn,\n"
+                               f"      int sc, int sn) {{\n"
+                               f"    int tmp;\n"
+                               f"    asm volatile(\"{group_asm_h(MBW, C0, SKC, PF, HN)}\"\n"
+                               f"        : {', '.join(outs)}\n"
+                               f"        : {', '.join(ins)}\n"
+                               f"        : \"memory\");\n"
+                               f"  }}\n}};\n")
+        for NB in sorted({nbufs(PF) for _, PF in forms}):
+            outs = [f'"+v"(aq[{k}])' for k in range(MBW)]
+            outs += [f'"+v"(bq[{j}][{q}])' for j in range(NB) for q in range(2)]
+            outs += [f'"+v"(acc[{k}][{n}])' for k in range(MBW) for n in range(2)]
+            out.append(f"template <>\nstruct KDrainH<{MBW}, {NB}> {{\n"
+                       f"  __device__ __forceinline__ static void run(az_f4 (&acc)[{MBW}][2], az_u4 (&aq)[{MBW}],\n"
+                       f"      az_u4 (&bq)[{NB}][2]) {{\n"
+                       f"    asm volatile(\"s_waitcnt vmcnt(0) lgkmcnt(0)\"\n"
+                       f"        : {', '.join(outs)}\n"
+                       f"        :\n"
+                       f"        : \"memory\");\n"
+                       f"  }}\n}};\n")
+    return count
+
+
 def operand_list(MBW, NB=2):
     outs = []
     for k in range(MBW):
@@ -396,6 +589,15 @@ def main():
     with open(OUT, "w") as fh:
         fh.write("\n".join(out))
     print(f"wrote {OUT}: {count} group variants")
+    out = ["// az_kloop_f16_asm.h -- GENERATED by gen_kloop_asm.py: do not edit.\n"
+           "// The one-term K-loop groups of AZ_CONV_F16 as hand-scheduled assembly (group_asm_h in the\n"
+           "// generator); included by az_tower16.hip.\n#pragma once\n\n#include \"az_kloop_asm.h\"\n\n"
+           "namespace az {\nnamespace {\n"]
+    count_h = emit_h(out)
+    out.append("}  // namespace\n}  // namespace az\n")
+    with open(OUT_H, "w") as fh:
+        fh.write("\n".join(out))
+    print(f"wrote {OUT_H}: {count_h} one-term group variants")
 
 
 if __name__ == "__main__":

@@ -24,6 +24,9 @@ class ConfigSelfPlay:
     base_seed = None             # None -> time-based like self_play.py:45
     cache_log2 = 26              # device plays_inferences entries (2^k, LRU; 2^26 = 4.6 GB for C4); 0 = no cache
     lanes = 0                    # slot groups on separate HIP streams (0 = auto)
+    conv_algo = 0                # the self-play engines' forward: 0 = fp32-accurate (engine.CONV_F16X2), 3 =
+                                 # engine.CONV_F16, one fp16 product per MAC (faster, policy within ~5e-4 of
+                                 # float64); MCTS, the arenas, the model's __call__ and training stay at 0
     chess_concurrent_games = 256 # chess device slots (BASELINE configs[4]: 2048 games / 8 GPUs)
     chess_max_plies = 512        # chess games stop (as draws) here; the reference has no cap
     chess_cache_log2 = 0         # chess plays_inferences entries (2^k, ~1.1 KB each; 0 = off: slower in

@@ -17,6 +17,7 @@ EVAL_HOST = 2  # include/az.h AZ_EVAL_HOST: a Python callable (Engine / ChessEng
 CONV_F16X2 = 0  # include/az.h AZ_CONV_F16X2 (default)
 CONV_DIRECT = 1
 CONV_F16X2_LAYERS = 2  # AZ_CONV_F16X2_LAYERS: the same arithmetic one layer per launch (A/B runs)
+CONV_F16 = 3  # AZ_CONV_F16: one fp16 product per MAC on the one-launch tower (opt-in, for self-play; not fp32-accurate)
 
 
 class AzError(RuntimeError):

@@ -10,9 +10,15 @@
   joblib fan-out (self_play.py:98-110).  Game g is the reference's play_game
   under np.random.seed(base_seed + g): MT19937(base_seed + g) past the
   2 H W 4 words its model construction draws (az_config.rng_skip).
+
+`python -m custom_alphazero.self_play --bench [--game chess]` compares the
+one-term fp16 forward (ConfigSelfPlay.conv_algo = engine.CONV_F16) with the
+default arithmetic: two engines that differ in conv_algo alone, in one
+process, in interleaved rounds (bench_conv_algo).
 """
 import json
 import os
+import sys
 import time
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
@@ -109,7 +115,7 @@ def _batched_engine(model, n_slots, sims=None):
              ConfigMCTS.dirichlet_noise_ratio)
     key = (c.board_height, c.board_width, c.n, c.gravity, sims, n_slots,
            synthetic, ConfigMCTS.index_move_greedy, ConfigMCTS.exploration_constant,
-           ConfigModel.depth, ConfigSelfPlay.cache_log2, ConfigSelfPlay.lanes, noise)
+           ConfigModel.depth, ConfigSelfPlay.cache_log2, ConfigSelfPlay.lanes, noise, ConfigSelfPlay.conv_algo)
     eng = _ENGINES.get(key)
     if eng is None:
         eng = az.Engine(c.board_height, c.board_width, c.n, c.gravity, sims, slots=n_slots,
@@ -119,6 +125,7 @@ def _batched_engine(model, n_slots, sims=None):
                         filters=ConfigModel.filters, depth=ConfigModel.depth,
                         value_hidden=ConfigModel.value_hidden, bn_epsilon=ConfigModel.bn_epsilon,
                         cache_log2=ConfigSelfPlay.cache_log2, lanes=ConfigSelfPlay.lanes, compact=True,
+                        conv_algo=ConfigSelfPlay.conv_algo,
                         dirichlet_noise=noise[0], dirichlet_alpha=noise[1], dirichlet_ratio=noise[2])
         eng.weights_key = None
         _ENGINES.clear()
@@ -161,7 +168,7 @@ def _chess_engine(model, n_slots, sims):
     # a callable is part of the key by identity: another callable gets another engine
     key = (sims, n_slots, synthetic, ConfigMCTS.index_move_greedy, ConfigMCTS.exploration_constant,
            ConfigModel.depth, ConfigSelfPlay.chess_max_plies, ConfigSelfPlay.chess_cache_log2,
-           id(model) if evaluator == az.EVAL_HOST else None, noise)
+           id(model) if evaluator == az.EVAL_HOST else None, noise, ConfigSelfPlay.conv_algo)
     eng = _CHESS_ENGINES.get(key)
     if eng is not None and evaluator == az.EVAL_HOST and eng.host_model is not model:
         eng = None  # (an id reused by a new object)
@@ -172,7 +179,7 @@ def _chess_engine(model, n_slots, sims):
                              exploration_constant=ConfigMCTS.exploration_constant,
                              filters=ConfigModel.filters, depth=ConfigModel.depth,
                              value_hidden=ConfigModel.value_hidden, bn_epsilon=ConfigModel.bn_epsilon,
-                             cache_log2=ConfigSelfPlay.chess_cache_log2,
+                             cache_log2=ConfigSelfPlay.chess_cache_log2, conv_algo=ConfigSelfPlay.conv_algo,
                              dirichlet_noise=noise[0], dirichlet_alpha=noise[1], dirichlet_ratio=noise[2])
         eng.weights_key = None
         eng.host_model = None
@@ -323,3 +330,105 @@ def save_samples(run_id: str, iteration: int, states, policies, rewards) -> str:
     out = os.path.join(path, ConfigPath.samples_file)
     np.savez(out, states=states, policies=policies, values=rewards)
     return out
+
+
+# ------------------------------------------------------------------ --bench
+def bench_conv_algo(game="connect_n", rounds=10, forwards=20, warm_moves=5, move_rounds=5, moves=5):
+    """Default arithmetic (conv_algo 0) against the one-term fp16 forward (3):
+    two engines, identical but for conv_algo, on the same init_weights(seed=0)
+    weights, timed in one process in interleaved rounds (numbers of separate
+    runs do not compare).  Connect-4: 100 sims, 4096 slots, depth 4, no cache,
+    compact, lanes auto; chess: 800 sims, 256 slots, depth 4.
+    Part 1, isolated forwards at two batch sizes: `rounds` rounds of
+    `forwards` forward calls per engine, each round ending synchronised (host
+    clock around the calls, their copies included, and the tower launches
+    alone by HIP events).  Part 2, a self-play window: `warm_moves` moves
+    each, then `move_rounds` alternating rounds of `moves` moves per engine.
+    -> one JSON-able dict: median and minimum per engine, and the ratios."""
+    from custom_alphazero.model.weights import init_weights, weight_spec
+    if game not in ("connect_n", "chess"):
+        raise ValueError(f"bench: game must be 'connect_n' or 'chess', got {game!r}")
+    chess = game == "chess"
+    algos = {"f16x2": az.CONV_F16X2, "f16": az.CONV_F16}
+    rng = np.random.RandomState(0)
+    if chess:
+        sims, slots, sizes = 800, 256, (128, 256)
+        spec = weight_spec(8, 8, 1880, ConfigModel.filters, 4, ConfigModel.value_hidden, 118)
+        x = (rng.rand(max(sizes), 8, 8, 118) < 0.1).astype(np.float32)
+        make = lambda a: az.ChessEngine(sims, slots=slots, evaluator=az.EVAL_NETWORK, depth=4, conv_algo=a)  # noqa: E731
+    else:
+        sims, slots, sizes = 100, 4096, (121, 4096)
+        spec = weight_spec(6, 7, 7, ConfigModel.filters, 4, ConfigModel.value_hidden)
+        x = np.eye(4, dtype=np.float32)[rng.randint(0, 3, size=(max(sizes), 6, 7))]
+        x[..., 3] = 1.0
+        make = lambda a: az.Engine(6, 7, 4, True, sims, slots=slots, evaluator=az.EVAL_NETWORK, depth=4,  # noqa: E731
+                                   cache_log2=0, compact=True, lanes=0, conv_algo=a)
+    weights = init_weights(spec, seed=0)
+    engines = {k: make(a) for k, a in algos.items()}
+    for eng in engines.values():
+        eng.set_weights(weights.items())
+
+    def summary(per_engine, rate=False):
+        """median and minimum per engine; the ratios are the one-term mode's speed over the default's
+        (times: f16x2 / f16, rates: f16 / f16x2) -- above 1 where it is faster"""
+        out = {k: {"median": float(np.median(v)), "min": float(np.min(v))} for k, v in per_engine.items()}
+        num, den = ("f16", "f16x2") if rate else ("f16x2", "f16")
+        for stat in ("median", "min"):
+            out[f"ratio_of_{stat}s"] = out[num][stat] / out[den][stat] if out[den][stat] else None
+        return out
+
+    rec = {"bench": "self_play_conv_algo", "game": game, "sims": sims, "slots": slots, "depth": 4,
+           "rounds": rounds, "forwards_per_round": forwards, "forward": {}}
+    for n in sizes:
+        for eng in engines.values():
+            eng.forward(x[:n])  # warm-up: first launch, allocations
+            eng.timer(True)
+        wall = {k: [] for k in engines}
+        tower = {k: [] for k in engines}
+        for _ in range(rounds):
+            for k, eng in engines.items():
+                before = eng.stats()
+                t0 = time.perf_counter()
+                for _ in range(forwards):
+                    eng.forward(x[:n])  # (returns with the outputs on the host: synchronised)
+                wall[k].append((time.perf_counter() - t0) / forwards * 1e3)
+                after = eng.stats()
+                tower[k].append((after["conv_ms"] - before["conv_ms"]) /
+                                max(after["conv_launches"] - before["conv_launches"], 1))
+        for eng in engines.values():
+            eng.timer(False)
+        rec["forward"][str(n)] = {"call_ms": summary(wall), "tower_launch_ms": summary(tower)}
+
+    budget = slots * (2 + (warm_moves + move_rounds * moves) // (2 if chess else 7))
+    for eng in engines.values():
+        eng.selfplay_begin(0, budget, 0)
+        eng.selfplay_step(warm_moves)
+    exp_s = {k: [] for k in engines}
+    games_s = {k: [] for k in engines}
+    errors = {}
+    for _ in range(move_rounds):
+        for k, eng in engines.items():
+            before = eng.stats()
+            t0 = time.perf_counter()
+            after = eng.selfplay_step(moves)  # (with stats: returns synchronised)
+            dt = time.perf_counter() - t0
+            exp_s[k].append((after["expansions"] - before["expansions"]) / dt)
+            games_s[k].append((after["games_done"] - before["games_done"]) / dt)
+            errors[k] = after["errors"]
+    rec["self_play"] = {"warm_moves": warm_moves, "rounds": move_rounds, "moves_per_round": moves,
+                        "expansions_per_s": summary(exp_s, rate=True), "games_per_s": summary(games_s, rate=True),
+                        "errors": errors}
+    for eng in engines.values():
+        eng.close()
+    return rec
+
+
+if __name__ == "__main__":
+    if "--bench" in sys.argv[1:]:
+        args = sys.argv[1:]
+        game = args[args.index("--game") + 1] if "--game" in args and args.index("--game") + 1 < len(args) \
+            else "connect_n"
+        print(json.dumps(bench_conv_algo(game=game)))
+    else:
+        raise SystemExit("the serving control plane (run id, sample queue over HTTP) is not part of this package: "
+                         "call play(run_id, ...) / run(run_id, ...), or run with --bench")

@@ -43,6 +43,19 @@ extern "C" {
                                 as two fp16 terms, three products per k-step (default); Connect-N
                                 runs the whole forward in one kernel, activations held in LDS */
 #define AZ_CONV_DIRECT 1     /* direct implicit GEMM on fp32 MFMA (exact fp32 FMA chains) */
+#define AZ_CONV_F16 3        /* opt-in, for self-play: ONE fp16 product per MAC (t0 * B0) on the one-launch tower --
+                                every conv the tower runs on the MFMA (stem, conv1, conv2, the 1x1 projection)
+                                sums fp16(activation) * fp16(prescaled folded weight) into the fp32 accumulator,
+                                in AZ_CONV_F16X2's k-step order (deterministic, batch invariant); a stored
+                                activation is its fp16 rounding, the last block's output reaches the heads
+                                unrounded, and the epilogues, range rescale, head convs, dense layers, softmax
+                                and tanh are AZ_CONV_F16X2's fp32.  The same weight packs (their main terms).
+                                One-hot boards are exact operands: forward(full_state(board)) stays bitwise
+                                the self-play queue's.  Not fp32-accurate: against float64 the policy is off
+                                by 5e-5 .. 5e-4 and the value by 1e-3 .. 3e-2 (depth 16) on the test
+                                networks (DESIGN.md "One-term fp16 forward").  Needs the tower: 1 <= depth <= 16,
+                                value_hidden <= 256 (Connect-N) and a layout for the board, else create /
+                                set_weights fail with AZ_E_INVALID -- no other arithmetic stands in for it */
 #define AZ_CONV_F16X2_LAYERS 2  /* AZ_CONV_F16X2's arithmetic one layer per launch (activations in
                                    HBM between layers; the round-2 path, kept for A/B runs) */
 
@@ -74,7 +87,10 @@ typedef struct az_config {
     int32_t conv_algo;             /* residual-tower 3x3 convs: AZ_CONV_F16X2 (0, default; depth <= 16,
                                       value_hidden <= 256), AZ_CONV_DIRECT (1) or AZ_CONV_F16X2_LAYERS
                                       (2; board width <= 16, activations within +-32752); same
-                                      layer, outputs within NET_TOL */
+                                      layer, outputs within NET_TOL.  AZ_CONV_F16 (3): opt-in one-term
+                                      fp16 arithmetic on the one-launch tower, for self-play -- NOT
+                                      within NET_TOL (see the define); 1 <= depth <= 16,
+                                      value_hidden <= 256 */
     int32_t lanes;                 /* self-play slot groups searched on separate HIP streams
                                       (0 = auto: 2 when slots >= 512); results do not depend on it */
     int32_t compact;               /* 1: after every self-play move the chosen child's subtree is

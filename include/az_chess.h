@@ -111,7 +111,9 @@ typedef struct az_chess_config {
     double bn_epsilon;
     int64_t arena_edges;          /* edges per arena half per slot (0 = 96 * mcts_iterations) */
     int32_t conv_algo;            /* AZ_CONV_F16X2 (default) / AZ_CONV_DIRECT: the tower and the
-                                     stem over the 118 planes zero-padded to 128 */
+                                     stem over the 118 planes zero-padded to 128; AZ_CONV_F16 (3):
+                                     the one-launch tower's one-term fp16 arithmetic (az.h; opt-in,
+                                     1 <= depth <= 16) */
     int32_t lanes;                /* slot groups searched on separate HIP streams (0 = auto: 2 from
                                      128 slots, else 1); results do not depend on it */
     int32_t cache_log2;           /* ABI 10: transposition cache entries = 2^cache_log2, the
