@@ -1167,18 +1167,17 @@ int simulate(az_chess_engine* e, CLane& L) {
   if (L.g.evaluator == AZ_EVAL_NETWORK) {
     // the one-launch tower builds the leaves' input planes itself (no encode
     // launch on the chain; az_nn.h TowerLeaves); the other forms read rows
-    const bool tower = e->net.algo == AZ_CONV_F16X2 && e->net.use_tower && e->net.tower;
+    const az::NetForm form = e->net.form;
+    const bool tower = form == az::NetForm::kTowerRows;
     az::TowerLeaves lv;
     lv.eval_slot = L.t.eval_slot;
     lv.leaf = L.t.leaf;
     lv.path_len = L.t.path_len;
     lv.initial = L.t.initial;
-    if (!tower) {
-      if (e->net.algo == AZ_CONV_F16X2)
-        encode_queue_kernel<true><<<std::min(S, 2048), 256, 0, s>>>(L.g, L.t, L.x);
-      else
-        encode_queue_kernel<false><<<std::min(S, 2048), 256, 0, s>>>(L.g, L.t, L.x);
-    }
+    if (form == az::NetForm::kLayers16)
+      encode_queue_kernel<true><<<std::min(S, 2048), 256, 0, s>>>(L.g, L.t, L.x);
+    else if (form == az::NetForm::kDirect)
+      encode_queue_kernel<false><<<std::min(S, 2048), 256, 0, s>>>(L.g, L.t, L.x);
     // history slots 0-5 (planes 0-83) are always empty in self-play (every
     // board's history is [0 x 6, start, board] or [0 x 7, start]): the stem
     // skips input chunks 0-1 (planes 0-63; they would add exact zeros) and
@@ -1272,13 +1271,14 @@ int az_chess_engine_create(int device, const az_chess_config* cfg, az_chess_engi
     return az::fail_abi(AZ_E_INVALID, "unknown evaluator");
   if (c.evaluator == AZ_EVAL_NETWORK && c.filters != 128)
     return az::fail_abi(AZ_E_INVALID, "network evaluator supports filters == 128 (ConfigModel.filters)");
-  if (c.conv_algo != AZ_CONV_F16X2 && c.conv_algo != AZ_CONV_DIRECT && c.conv_algo != AZ_CONV_F16X2_LAYERS &&
-      c.conv_algo != AZ_CONV_F16)
-    return az::fail_abi(AZ_E_INVALID,
-                        "conv_algo must be AZ_CONV_F16X2, AZ_CONV_DIRECT, AZ_CONV_F16X2_LAYERS or AZ_CONV_F16");
-  // the one-term arithmetic exists on the one-launch tower only: no other form stands in for it
-  if (c.conv_algo == AZ_CONV_F16 && (c.depth < 1 || c.depth > az::kTowerMaxDepth))
-    return az::fail_abi(AZ_E_INVALID, "AZ_CONV_F16 needs the one-launch tower: 1 <= depth <= 16");
+  az::NetRequest req;  // (one tile height: lanes stay 1)
+  req.conv_algo = c.conv_algo;
+  req.in_ch = AZ_CHESS_PLANES;
+  req.H = req.W = 8, req.A = AZ_CHESS_ACTIONS;
+  req.depth = c.depth, req.hidden = c.value_hidden;
+  req.network_evaluator = c.evaluator == AZ_EVAL_NETWORK;
+  if (const az::NetStatus bad = az::check_net_request(req); bad.code != AZ_OK)
+    return az::fail_abi(bad.code, bad.message);
   if (c.max_plies < 0 || c.arena_edges < 0 || c.depth < 0 || c.value_hidden < 1)
     return az::fail_abi(AZ_E_INVALID, "negative bound");
   if ((int64_t)c.slots * 64 * 512 >= (1ll << 31))
@@ -1369,21 +1369,7 @@ int az_chess_engine_create(int device, const az_chess_config* cfg, az_chess_engi
   if ((rc = az::cache_create(e->mem, e->cache, c.cache_log2, 28, kPayFloats, 0))) return cleanup(rc);
   t.leaf_pay = nullptr;
   if (e->cache.enabled && (rc = e->mem.alloc(&t.leaf_pay, S * kPayFloats, false))) return cleanup(rc);
-  e->net.depth = c.depth;
-  // depth 0: the fp16x2 chain runs the heads' 1x1 convs inside the last
-  // block's conv2, so a tower without blocks takes the fp32 MFMA path
-  // (AZ_CONV_F16: AZ_CONV_F16X2's packs and input rows, the tower's one-term kernels -- net.terms)
-  e->net.algo = c.depth == 0 ? AZ_CONV_DIRECT
-                             : (c.conv_algo == AZ_CONV_F16X2_LAYERS || c.conv_algo == AZ_CONV_F16 ? AZ_CONV_F16X2
-                                                                                                  : c.conv_algo);
-  e->net.terms = c.conv_algo == AZ_CONV_F16 ? 1 : 3;
-  // AZ_CONV_F16X2: the stem, the tower and the heads' 1x1 convs in one launch
-  // (tower16_kernel's input-row form) when the network fits it, else the
-  // per-layer conv16 chain (AZ_CONV_F16X2_LAYERS forces the chain)
-  e->net.use_tower = (c.conv_algo == AZ_CONV_F16X2 || c.conv_algo == AZ_CONV_F16) && c.depth >= 1 &&
-                     c.depth <= az::kTowerMaxDepth;
-  e->net.board_h = e->net.board_w = 8;
-  e->net.hidden = c.value_hidden;
+  e->net.req = req;  // the forward's form: load_network, once the weights and the device are known
   e->net.err = t.stats + az::kStatErrors;
   if (c.lanes < 0) return cleanup(az::fail_abi(AZ_E_INVALID, "lanes must be >= 0"));
   // auto = 2 from 128 games: a lane's simulation is a latency-bound chain of
@@ -1438,8 +1424,7 @@ int az_chess_engine_set_weights(az_chess_engine* e, const az_tensor* tensors, in
     AZ_TRY(az::cache_clear(e->cache, nullptr));
     AZ_HIP(hipStreamSynchronize(nullptr));
   }
-  return az::load_network(e->net, tensors, n, AZ_CHESS_PLANES, 64, AZ_CHESS_ACTIONS, e->cfg.bn_epsilon,
-                          e->mem);
+  return az::load_network(e->net, tensors, n, e->cfg.bn_epsilon, e->mem);
 }
 
 int az_chess_forward(az_chess_engine* e, const float* x, int n, float* probs, float* values) {
@@ -1455,7 +1440,7 @@ int az_chess_forward(az_chess_engine* e, const float* x, int n, float* probs, fl
     float* staging = static_cast<float*>(e->act[2]);
     AZ_HIP(hipMemcpyAsync(staging, x + (size_t)off * 64 * AZ_CHESS_PLANES,
                           (size_t)m * 64 * AZ_CHESS_PLANES * sizeof(float), hipMemcpyHostToDevice, e->stream));
-    az::launch_pad_rows(staging, m * 64, AZ_CHESS_PLANES, e->x, e->net.algo == AZ_CONV_F16X2, e->stream);
+    az::launch_pad_rows(staging, m * 64, AZ_CHESS_PLANES, e->x, e->net.form != az::NetForm::kDirect, e->stream);
     az::launch_forward(e->net, e->x, nullptr, m, 8, 8, AZ_CHESS_ACTIONS, e->act[0], e->act[1], e->act[2],
                        e->probs, e->values, e->stream, e->timer.enabled ? &e->timer : nullptr);
     AZ_HIP(hipGetLastError());
@@ -1505,8 +1490,7 @@ int az_chess_stats(az_chess_engine* e, az_stats* st) {
   unsigned long long h[az::kStatCount];
   if ((rc = az::read_common_stats(st, h, e->t.stats, e->t.game_id, e->g.slots, e->cache)))
     return rc;
-  st->issued_flop_per_board = e->net.use_tower && e->net.tower ? e->net.layout.main.issued_flop_per_board : 0.0;
-  if (e->net.terms == 1) st->issued_flop_per_board /= 3;  // AZ_CONV_F16 issues one of the three products
+  st->issued_flop_per_board = az::issued_flop_per_board(e->net.form, e->net.terms, e->net.layout).main;
   st->tower_small_max_boards = -1;  // (chess: one tile height)
   std::vector<az::ConvTimer*> timers = {&e->timer};
   for (CLane* L : e->lanes) timers.push_back(&L->timer);

@@ -5,6 +5,7 @@
 
 #include "../../include/az.h"
 #include "az_device.h"
+#include "az_net_form.h"
 #include "az_tower_layout.h"
 
 namespace az {
@@ -87,24 +88,19 @@ void launch_tower16_rows(const TowerNet* net, const TowerLayout& L, const void* 
                          hipStream_t s, const TowerLeaves* leaves = nullptr, int terms = 3);
 
 // Folded (BatchNorm-in) weights resident in HBM, packed for the kernels (not
-// Keras layouts).  AZ_CONV_F16X2 (default): conv16_kernel packs (fp16 term
-// pairs, az_conv16.hip) and split16 activations; AZ_CONV_DIRECT: fp32 MFMA
-// fragment packs ([chunk][tile][q][lane] float4) and fp32 activations.
+// Keras layouts): conv16_kernel packs (fp16 term pairs, az_conv16.hip) for
+// the fp16x2 forms, which keep split16 activations; fp32 MFMA fragment packs
+// ([chunk][tile][q][lane] float4) for NetForm::kDirect, fp32 activations.
 struct NetDev {
-  int filters = 128, depth = 0, hidden = 256;
-  int algo = 0;             // AZ_CONV_F16X2 / AZ_CONV_DIRECT (one algorithm for every forward)
-  bool use_tower = false;   // Connect-N, AZ_CONV_F16X2: the whole forward in tower16_kernel (else per layer)
-  int terms = 3;            // fp16 products per MAC on the tower: 3, or 1 (AZ_CONV_F16: algo stays AZ_CONV_F16X2
-                            // -- the same packs and input rows -- and the launches take the one-term kernels)
-  bool tower_natural_order = false;  // az_config.tower_natural_order: no slot plan (A/B, bitwise the same)
-  TowerNet* tower = nullptr;  // device copy of the tower's view (load_network)
-  TowerLayout layout;         // what it was filled from: tile heights, staging, issued FLOP (az_stats)
-  int lanes = 1;              // the engine's lanes (streams whose towers share the CUs): the dual threshold
-  int in_ch = 4;            // input planes: 4 (Connect-N) or 118 (chess, padded to F)
-  int board_h = 0, board_w = 0;  // Connect-N board (the tower's slot plan)
-  float* stem_w = nullptr;  // in_ch == 4: [36][F] (k = tap*4 + c), VALU stem kernels
+  NetRequest req;  // what the engine was created with (lanes once they exist; load_network adds the device's CUs)
+  // plan_network's answer to it, written by load_network: one form for every forward
+  NetForm form = NetForm::kDirect;
+  int terms = 3;              // fp16 products per MAC on the tower: 3, or 1 (AZ_CONV_F16)
+  TowerLayout layout;         // the tower forms': tile heights, staging, issued FLOP (az_stats)
+  TowerNet* tower = nullptr;  // device copy of the tower's view, filled from layout
+  float* stem_w = nullptr;  // req.in_ch == 4: [36][F] (k = tap*4 + c), VALU stem kernels
   float* stem_b = nullptr;  // [F]
-  // in_ch > 4 (chess): the stem is one more 3x3 conv over the zero-padded planes
+  // req.in_ch > 4 (chess): the stem is one more 3x3 conv over the zero-padded planes
   uint16_t* stem_k = nullptr;  // conv16 pack (36 k-steps)
   float stem_scale = 1.f;      // its 2^(e-12)
   float* stem_d = nullptr;     // direct-kernel fragments [9F x F]
@@ -221,13 +217,13 @@ size_t conv16_lds_bytes(int MB, int W, bool res);
 int conv16_prescale(const double* w, size_t n, const double* w2, size_t n2);
 // weights [3][3][cin_n][128] (+ 1x1 residual [128][128]) -> uint16 fp16 bits
 void conv16_pack(const double* w3, int cin_n, const double* wr, int e, std::vector<uint16_t>& out);
-// Folds and uploads the network weights (Keras names, model/weights.py);
-// device buffers are allocated from `owned` (az_engine.hip; az_host.h)
+// az_net_load.hip: folds the network weights (Keras names, model/weights.py), uploads them packed
+// for the kernels, and plans net.req's forward (plan_network: form, terms, layout; the tower's view
+// where the form is one); device buffers are allocated from `owned` (az_host.h)
 struct DeviceAllocs;
-int load_network(NetDev& net, const ::az_tensor* tensors, int n, int in_ch, int HW, int A,
-                 double eps, DeviceAllocs& owned);
+int load_network(NetDev& net, const ::az_tensor* tensors, int n, double eps, DeviceAllocs& owned);
 // x: [n][HW][4] fp32 (in_ch == 4), or the zero-padded planes [n][HW][F] (in_ch > 4) as split16 rows
-// (AZ_CONV_F16X2) or fp32 (AZ_CONV_DIRECT); count (device int, may be null -> n_max) is the live
+// (the fp16x2 forms) or fp32 (NetForm::kDirect); count (device int, may be null -> n_max) is the live
 // batch; boards (optional): one-hot input straight from the eval queue's boards (bitwise the same
 // outputs as encoding them into x first); stem_first_chunk: input planes below 32 * it are known zero
 void launch_forward(const NetDev& net, const void* x, const int* count, int n_max, int H, int W,

@@ -8,7 +8,7 @@
 //   policy conv1x1 F->2 + BN + ReLU, flatten HWC, Dense(A) softmax
 //   value  conv1x1 F->1 + BN + ReLU, flatten, Dense(256) ReLU, Dense(1) tanh
 // BatchNorm runs with moving statistics (call(training=False)); the engine
-// folds it into the conv weights on the host (az_engine.hip).
+// folds it into the conv weights on the host (az_net_load.hip).
 //
 // Kernels (each one's roofline in DESIGN.md):
 //   encode_boards    Board.full_state for the eval queue (HBM/latency bound)
@@ -212,7 +212,7 @@ __global__ __launch_bounds__(256) void stem_board_kernel(const Board* __restrict
 //     chunks, chunk j of slab row r stored at j ^ (r & 15): the 16 distinct
 //     rows a ds_read_b128 lane group touches land on 16 distinct bank quads.
 //   * B: weights are pre-packed on the host in MFMA fragment order
-//     ([chunk][tile][q][lane] float4, az_engine.hip pack_fragments) and stream
+//     ([chunk][tile][q][lane] float4, az_net_load.hip pack_fragments) and stream
 //     straight into registers with fully coalesced 1 KiB loads, one 32-wide K
 //     chunk ahead -- no LDS, no barrier in the K loop.
 // v_mfma_f32_32x32x2_f32 is an exact f32 FMA chain; inside a chunk lane half
@@ -706,15 +706,15 @@ void launch_forward(const NetDev& net, const void* x, const int* count, int n_ma
   if (n_max <= 0) return;
   const int HW = H * W;
   constexpr int F = 128;
-  const bool f16 = net.algo == AZ_CONV_F16X2;
-  if (f16 && net.use_tower && net.in_ch == 4 && net.tower) {  // the whole forward in one launch
+  const int depth = net.req.depth, hidden = net.req.hidden;
+  if (net.form == NetForm::kTower) {  // the whole forward in one launch
     if (timer) timer->begin(s);
     launch_tower16(net.tower, net.layout, boards, boards ? nullptr : static_cast<const float4*>(x), count, n_max, H, W,
                    A, probs, values, net.err, s, net.terms);
     if (timer) timer->end(s, 1);
     return;
   }
-  if (f16 && net.use_tower && net.in_ch > 4 && net.tower && HW == 64 && A > kMaxActions) {
+  if (net.form == NetForm::kTowerRows) {
     // chess: the stem, the tower and the heads' 1x1 convs in one launch
     // (features into act_a), then the dense heads as below
     if (timer) timer->begin(s);
@@ -725,10 +725,11 @@ void launch_forward(const NetDev& net, const void* x, const int* count, int n_ma
                    net.pd_b, net.v1_w, net.v1_b, net.v2_w, net.v2_b};
     const float4* feat = static_cast<const float4*>(act_a);
     launch_policy_dense(feat, net.pd_wt, net.pd_b, count, n_max, HW, A, probs, s);
-    heads_tail_kernel<<<std::min(n_max, 2048), kTailThreads, 0, s>>>(feat, hw, count, n_max, HW, A, net.hidden, probs,
+    heads_tail_kernel<<<std::min(n_max, 2048), kTailThreads, 0, s>>>(feat, hw, count, n_max, HW, A, hidden, probs,
                                                                      values);
     return;
   }
+  const bool f16 = net.form == NetForm::kLayers16;  // the per-layer chains: fp16x2, or (kDirect) fp32 MFMA
   Conv16Args ca;
   ca.count = count;
   ca.n_max = n_max;
@@ -742,7 +743,7 @@ void launch_forward(const NetDev& net, const void* x, const int* count, int n_ma
   const long rows_max = (long)n_max * HW;
   ca.mb = rows_max <= 24576 ? 2 : (rows_max <= 65536 ? 3 : 4);
   ca.err = net.err;
-  if (net.in_ch > 4) {
+  if (net.req.in_ch > 4) {
     // chess: 118 input planes zero-padded to F, the stem is one more 3x3 conv;
     // stem_first_chunk: input chunks (32 planes) before it are known zero and
     // skipped -- they would add exact zeros (chess self-play: planes 0-63)
@@ -782,8 +783,8 @@ void launch_forward(const NetDev& net, const void* x, const int* count, int n_ma
   void* mid = act_b;
   void* nxt = act_c;
   if (timer) timer->begin(s);
-  for (int d = 0; d < net.depth; ++d) {
-    const bool last = d == net.depth - 1;
+  for (int d = 0; d < depth; ++d) {
+    const bool last = d == depth - 1;
     if (f16) {
       Conv16Args a = ca;
       a.in = cur;
@@ -813,25 +814,25 @@ void launch_forward(const NetDev& net, const void* x, const int* count, int n_ma
     cur = nxt;
     nxt = t;
   }
-  if (timer) timer->end(s, 2 * net.depth);
+  if (timer) timer->end(s, 2 * depth);
   const float* act = static_cast<const float*>(cur);  // f16: the fused head features; direct: block output
   HeadWeights hw{net.pc_w, net.pc_b, net.vc_w, net.vc_b, net.pd_w,
                  net.pd_b, net.v1_w, net.v1_b, net.v2_w, net.v2_b};
-  const size_t wbytes = (size_t)(2 * HW * A + HW * net.hidden) * sizeof(float);
+  const size_t wbytes = (size_t)(2 * HW * A + HW * hidden) * sizeof(float);
   const bool stage = wbytes <= 64 * 1024;
   const int hblocks = stage ? std::min((n_max + 3) / 4, 512) : (n_max + 3) / 4;
 #define AZ_HEADS(FEAT_, STAGE_)                                                                      \
   heads_kernel<F, FEAT_, STAGE_, kMaxActions><<<hblocks, 256, STAGE_ ? wbytes : 0, s>>>(           \
-      act, hw, count, n_max, HW, A, net.hidden, probs, values)
+      act, hw, count, n_max, HW, A, hidden, probs, values)
   if (A > kMaxActions) {  // chess: 1880 actions
     if (f16 && HW == 64 && A <= kTailThreads * kTailPer && net.pd_wt) {
       const float4* feat = reinterpret_cast<const float4*>(act);
       launch_policy_dense(feat, net.pd_wt, net.pd_b, count, n_max, HW, A, probs, s);
-      heads_tail_kernel<<<std::min(n_max, 2048), kTailThreads, 0, s>>>(feat, hw, count, n_max, HW, A,
-                                                                       net.hidden, probs, values);
+      heads_tail_kernel<<<std::min(n_max, 2048), kTailThreads, 0, s>>>(feat, hw, count, n_max, HW, A, hidden,
+                                                                       probs, values);
     } else {
-      heads_kernel<F, false, false, 2048><<<(n_max + 3) / 4, 256, 0, s>>>(act, hw, count, n_max, HW, A,
-                                                                          net.hidden, probs, values);
+      heads_kernel<F, false, false, 2048><<<(n_max + 3) / 4, 256, 0, s>>>(act, hw, count, n_max, HW, A, hidden,
+                                                                          probs, values);
     }
   } else if (f16) {
     if (stage) AZ_HEADS(true, true); else AZ_HEADS(true, false);

@@ -2,7 +2,7 @@
 INFRASTRUCTURE, on forward_ref / chess_forward_ref).
 
   restate16      the forward in numpy with the mode's rounding: BN folded into
-                 each conv in float64 (az_engine.hip fold_unit), the folded
+                 each conv in float64 (az_net_load.hip fold_unit), the folded
                  weights prescaled by 2^-e (conv16_prescale; conv2 and its 1x1
                  projection jointly) and rounded float64 -> float32 -> float16,
                  the input and every activation kept between convs (stem,

@@ -13,6 +13,8 @@
                   eighth of what the mildest of them does to that output
   CASES           the board / depth / hidden table, one row per tower layout
                   (tests/native/tower_layout_check.cpp states which)
+  FALLBACK_CASES  networks the default conv_algo gives a per-layer form
+                  (tests/native/net_form_check.cpp states which)
   case_data       everything of one case, computed once per process
 
 Nothing here touches libaz.
@@ -70,7 +72,16 @@ CASES = [
     _case(16, 8, True, 1),
     _case(2, 20, True, 1, n=2),      # W > 16 (the per-layer fp16 kernels refuse it)
 ]
-CASE_BY_NAME = {c.name: c for c in CASES}
+# what AZ_CONV_F16X2 runs where the one-launch tower does not take the network (csrc/az_net_form.h):
+# tests/test_net_form_cpu.py asserts the forms, tests/test_forward_forms_gpu.py runs them
+FALLBACK_CASES = [
+    _case(3, 3, True, 17, n=3),        # depth > 16: the per-layer fp16x2 chain
+    _case(3, 3, True, 1, 300, n=3),    # hidden > 256: the same
+    _case(2, 20, True, 17, n=2),       # depth > 16 and W > 16: the fp32 MFMA chain
+    _case(3, 3, True, 0, n=3),         # no block: the fp32 MFMA chain.  No block conv either, so mutant M3
+                                       # does not exist here: it is left out of this case's minima
+]
+CASE_BY_NAME = {c.name: c for c in CASES + FALLBACK_CASES}
 # boards of 33-48 cells: 128-row tiles of three, or 96-row tiles of two for small launches
 DUAL_CASES = ("6x7g_d4_h256", "6x7n_d2_h256", "6x7g_d2_h1", "6x7g_d2_h100", "6x7g_d2_h255", "6x6g_d2_h64",
               "2x20g_d1_h256")
@@ -247,17 +258,24 @@ def layouts():
 def run_layout_check(tmp, args):
     """Builds tests/native/tower_layout_check.cpp in tmp against libaz.so and
     the library's layout header, runs it with args -> its stdout."""
-    exe = os.path.join(tmp, "tower_layout_check")
+    return run_native_check(tmp, "tower_layout_check", args)
+
+
+def run_native_check(tmp, program, args):
+    """Builds tests/native/<program>.cpp in tmp against libaz.so and the
+    library's host-only headers, runs it with args -> its stdout."""
+    exe = os.path.join(tmp, program)
     subprocess.run(["g++", "-O1", "-std=c++17", "-I", os.path.join(REPO, "custom-alphazero_amd", "csrc"), "-o", exe,
-                    os.path.join(REPO, "tests", "native", "tower_layout_check.cpp"),
+                    os.path.join(REPO, "tests", "native", program + ".cpp"),
                     os.path.join(LIB, "libaz.so"), f"-Wl,-rpath,{LIB}"], check=True)
     return subprocess.run([exe] + args, check=True, capture_output=True, text=True).stdout
 
 
 @functools.lru_cache(maxsize=None)
 def case_data(name):
-    """One case's batch, weights, float64 reference, float32 error, mutant
-    errors and tolerances (a dict; computed once, treat as read-only)."""
+    """One case's (of CASES or FALLBACK_CASES) batch, weights, float64
+    reference, float32 error, mutant errors, the mutants that move each output
+    and the tolerances (a dict; computed once, treat as read-only)."""
     c = CASE_BY_NAME[name]
     x = make_batch(c.H, c.W)
     w, h = _lively(c.H, c.W, c.gravity, c.depth, c.hidden, x, 0)
@@ -268,8 +286,11 @@ def case_data(name):
     mut_p, mut_v = {}, {}
     for m, (mp, mv) in mutants(w, x, c.depth, h).items():
         mut_p[m], mut_v[m] = float(np.abs(mp - p).max()), float(np.abs(mv - v).max())
+    # (M3 drops a tap of the last block's conv2: without a block it is the unmutated forward)
+    moves_p, moves_v = ([m for m in ms if m != "M3" or c.depth > 0] for ms in (MOVES_POLICY, MOVES_VALUE))
     d = dict(case=c, x=x, w=w, p=p, v=v, e32_p=e32_p, e32_v=e32_v, mut_p=mut_p, mut_v=mut_v,
-             tol_p=min(mut_p[m] for m in MOVES_POLICY) / 8, tol_v=min(mut_v[m] for m in MOVES_VALUE) / 8,
+             moves_p=moves_p, moves_v=moves_v,
+             tol_p=min(mut_p[m] for m in moves_p) / 8, tol_v=min(mut_v[m] for m in moves_v) / 8,
              dense1_active=float((z > 0).mean()), dense1_units_alive=float((z > 0).any(axis=0).mean()))
     for a in (x, p, v):
         a.setflags(write=False)

@@ -15,6 +15,7 @@ import keras_ref
 from custom_alphazero.model.weights import init_weights, weight_spec
 
 NAMES = [c.name for c in fr.CASES]
+FALLBACK_NAMES = [c.name for c in fr.FALLBACK_CASES]
 
 
 @pytest.mark.skipif(not fr.have_lib(), reason="libaz.so not built")
@@ -108,7 +109,7 @@ def test_old_weights_leave_the_value_head_dead():
     assert fr.case_data("6x7g_d4_h256")["v"].std() > 0.2
 
 
-@pytest.mark.parametrize("name", NAMES)
+@pytest.mark.parametrize("name", NAMES + FALLBACK_NAMES)
 def test_case_is_lively_and_separates_the_mutants(name):
     d = fr.case_data(name)
     c, p, v = d["case"], d["p"], d["v"]
@@ -124,10 +125,14 @@ def test_case_is_lively_and_separates_the_mutants(name):
         assert d["dense1_units_alive"] == 1.0
     else:
         assert d["dense1_active"] >= 0.25, d["dense1_active"]  # of the (board, unit) pre-activations
-    for m in fr.MOVES_POLICY:
+    no_block = ["M3"] if c.depth == 0 else []  # (M3 mutates the last block's conv2)
+    assert d["moves_p"] == [m for m in fr.MOVES_POLICY if m not in no_block]
+    assert d["moves_v"] == [m for m in fr.MOVES_VALUE if m not in no_block]
+    for m in d["moves_p"]:
         assert d["mut_p"][m] > d["tol_p"], (m, d["mut_p"][m], d["tol_p"])
-    for m in fr.MOVES_VALUE:
+    for m in d["moves_v"]:
         assert d["mut_v"][m] > d["tol_v"], (m, d["mut_v"][m], d["tol_v"])
+    assert d["tol_p"] > 0 and d["tol_v"] > 0
     assert d["mut_p"]["M4"] == 0.0 and d["mut_v"]["M5"] == 0.0  # each head's mutant is its own
     assert d["tol_p"] >= 8 * d["e32_p"], (d["tol_p"], d["e32_p"])
     assert d["tol_v"] >= 8 * d["e32_v"], (d["tol_v"], d["e32_v"])
