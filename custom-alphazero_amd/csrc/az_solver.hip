@@ -13,59 +13,19 @@
 #include <string>
 #include <vector>
 
-#include "../../include/az.h"
-#include "az_host.h"
-#include "az_solver.h"
+#include "az_solver_handle.h"
 
 using az::fail_abi;
 namespace sv = az::solver;
+using sv::kMaxLanes;
+using sv::kWave;
+using sv::Queue;
 
 namespace {
 
-constexpr int kWave = 64;
-// 1024 waves: one a SIMD on the MI355X's 256 CUs.  A wave is its own workgroup,
-// so a handful of jobs still spreads over the chip.
-constexpr int kMaxLanes = 1024 * kWave;
-// Steps a lane runs per launch.  With every lane busy on 7x6 a lane ran 78.7 k
-// steps/s on the MI355X, so a launch takes 26 ms: short enough to share the
-// device.  512 and 8192 steps gave the same throughput within 2 %
-// (DESIGN.md "Exact solver").
-constexpr int kDefaultSteps = 2048;
-// Positions with fewer stones are split on the host.  8 serves the boards the
-// solver finishes from the empty board (up to about 6x5); a 7x6 position that
-// shallow is out of reach either way (DESIGN.md has the sweep).
-constexpr int kDefaultSplit = 8;
-constexpr int64_t kDefaultMaxJobs = 1 << 20;
 constexpr int kDrained = -2;  // Lane::job of an idle lane that found the queue empty
 
-struct Queue {
-  int32_t next;  // the next job to hand out
-  int32_t done;  // jobs retired
-};
-
 }  // namespace
-
-struct az_solver {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  sv::Geo geo{};
-  sv::Table table{};
-  int tt_log2 = 0;
-  int split_stones = kDefaultSplit;
-  int64_t max_jobs = kDefaultMaxJobs;
-  int steps = kDefaultSteps;
-  sv::Lane* lanes = nullptr;     // [kMaxLanes]
-  uint64_t* st_moves = nullptr;  // [H*W][kMaxLanes]
-  uint32_t* st_ab = nullptr;     // [H*W][kMaxLanes]
-  Queue* queue = nullptr;
-  az::DeviceAllocs mem;
-  // per call, grown on demand
-  size_t job_cap = 0;
-  sv::Pos* jobs = nullptr;
-  int32_t* jscore = nullptr;
-  uint8_t* jstatus = nullptr;
-  int64_t* jnodes = nullptr;
-};
 
 namespace az {
 namespace solver {
@@ -116,6 +76,7 @@ namespace {
 void free_solver(az_solver* s) {
   (void)hipSetDevice(s->device);
   if (s->stream) (void)hipStreamSynchronize(s->stream);
+  sv::book::drop(s);
   s->mem.free_all();
   for (void* p : {(void*)s->jobs, (void*)s->jscore, (void*)s->jstatus, (void*)s->jnodes})
     if (p) (void)hipFree(p);
@@ -136,8 +97,10 @@ int grow_jobs(az_solver* s, size_t n) {
   return AZ_OK;
 }
 
+}  // namespace
+
 // the jobs' exact scores on the device: relaunch until all are retired
-int run_jobs(az_solver* s, const std::vector<sv::Pos>& jobs, int64_t budget, std::vector<int32_t>& score,
+int az::solver::run_jobs(az_solver* s, const std::vector<sv::Pos>& jobs, int64_t budget, std::vector<int32_t>& score,
              std::vector<uint8_t>& status, std::vector<int64_t>& nodes) {
   const size_t n = jobs.size();
   score.assign(n, 0), status.assign(n, AZ_SOLVER_UNSOLVED), nodes.assign(n, 0);
@@ -174,6 +137,8 @@ int run_jobs(az_solver* s, const std::vector<sv::Pos>& jobs, int64_t budget, std
   for (size_t i = 0; i < n; ++i) score[order[i]] = sc[i], status[order[i]] = stt[i], nodes[order[i]] = nd[i];
   return AZ_OK;
 }
+
+namespace {
 
 std::string limits_text() {
   return "the solver takes gravity boards with H, W >= 2, W <= 16, W * (H + 1) <= 56 and 2 <= n <= max(H, W)";
@@ -246,23 +211,36 @@ int az_solver_solve(az_solver* s, const int8_t* boards, int64_t count, int64_t n
     return fail_abi(AZ_E_INVALID, "az_solver_solve: bad arguments");
   if (node_budget <= 0) return fail_abi(AZ_E_INVALID, "az_solver_solve: node_budget must be > 0");
   const sv::Geo& g = s->geo;
-  sv::Plan plan;
+  std::vector<sv::Pos> roots((size_t)count);
   for (int64_t i = 0; i < count; ++i) {
-    sv::Pos p;
-    const std::string why = sv::parse_board(g, boards + (size_t)i * g.HW, &p);
+    const std::string why = sv::parse_board(g, boards + (size_t)i * g.HW, &roots[i]);
     if (!why.empty()) return fail_abi(AZ_E_INVALID, "az_solver_solve: board " + std::to_string(i) + " " + why);
-    sv::plan_add(plan, g, p, s->split_stones, s->max_jobs);
+  }
+  AZ_HIP(hipSetDevice(s->device));
+  // a finished book answers the roots it holds; the others go on as without one
+  std::vector<uint8_t> hit;
+  std::vector<int32_t> book_score;
+  if (sv::book::lookup_depth(s) >= 0) AZ_TRY(sv::book::lookup(s, roots, hit, book_score));
+  sv::Plan plan;
+  std::vector<int64_t> root_of((size_t)count, -1);  // board -> its root in the plan
+  for (int64_t i = 0; i < count; ++i) {
+    if (!hit.empty() && hit[i]) continue;
+    root_of[i] = (int64_t)plan.roots.size();
+    sv::plan_add(plan, g, roots[i], s->split_stones, s->max_jobs);
     if (plan.jobs.size() > ((size_t)1 << 30))
       return fail_abi(AZ_E_INVALID, "az_solver_solve: more than 2^30 jobs in one call");
   }
-  AZ_HIP(hipSetDevice(s->device));
   std::vector<int32_t> jscore;
   std::vector<uint8_t> jstatus;
   std::vector<int64_t> jnodes;
-  AZ_TRY(run_jobs(s, plan.jobs, node_budget, jscore, jstatus, jnodes));
+  AZ_TRY(sv::run_jobs(s, plan.jobs, node_budget, jscore, jstatus, jnodes));
   for (int64_t i = 0; i < count; ++i) {
-    const bool ok =
-        sv::plan_result(plan, g, (size_t)i, jscore.data(), jstatus.data(), jnodes.data(), scores + i, nodes + i);
+    if (root_of[i] < 0) {
+      scores[i] = book_score[i], status[i] = AZ_SOLVER_SOLVED, nodes[i] = 0;
+      continue;
+    }
+    const bool ok = sv::plan_result(plan, g, (size_t)root_of[i], jscore.data(), jstatus.data(), jnodes.data(),
+                                    scores + i, nodes + i);
     status[i] = ok ? AZ_SOLVER_SOLVED : AZ_SOLVER_UNSOLVED;
   }
   return AZ_OK;

@@ -70,13 +70,17 @@ class ConfigMCTS:
 
 class ConfigSolver:
     """The exact Connect-N solver on the device (engine.Solver, exact_solvers/):
-    an addition; the reference has ConfigPath.connect4_solver_bin and an opening
-    book instead.  node_budget = 0 leaves the solver off: use_solver and
-    evaluate_with_solver then raise NotImplementedError as before."""
+    an addition; the reference has ConfigPath.connect4_solver_bin and a 7x6
+    opening book.  Here positions are searched within node_budget, and
+    book_path names an opening book of this project's own (built with `python -m
+    custom_alphazero.exact_solvers --build-book`) that answers the shallow
+    positions a budget does not reach.  node_budget = 0 leaves the solver off:
+    use_solver and evaluate_with_solver then raise NotImplementedError as before."""
     node_budget = 0        # search nodes a position may take before it counts as unsolved; 0 = solver off
     tt_log2 = 24           # transposition table entries (2^k words of 8 bytes)
     split_stones = 0       # positions with fewer stones are split on the host (0 = the library's default)
     max_jobs = 0           # largest frontier of a split position (0 = the library's default)
+    book_path = ""         # a finished opening book of the board's (H, W, n) to load; "" = none
     device = 0
 
 

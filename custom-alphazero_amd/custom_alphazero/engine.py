@@ -6,6 +6,7 @@ tree and worker seams all land here.
 """
 import ctypes
 import os
+import time
 
 import numpy as np
 
@@ -117,6 +118,8 @@ EXPORTED = (
     "az_chess_replay_clear", "az_chess_replay_gather", "az_trainer_step_replay",
     # the exact Connect-N solver (include/az.h)
     "az_solver_create", "az_solver_destroy", "az_solver_clear", "az_solver_configure", "az_solver_solve",
+    "az_solver_book_begin", "az_solver_book_solve", "az_solver_book_finish", "az_solver_book_save",
+    "az_solver_book_load", "az_solver_book_info", "az_solver_book_level",
 )
 
 _lib = None
@@ -217,6 +220,13 @@ def load_library():
         "az_solver_clear": (ctypes.c_int, [P]),
         "az_solver_configure": (ctypes.c_int, [P, ctypes.c_int, I64, ctypes.c_int]),
         "az_solver_solve": (ctypes.c_int, [P, P, I64, I64, P, P, P]),
+        "az_solver_book_begin": (ctypes.c_int, [P, ctypes.c_int, P]),
+        "az_solver_book_solve": (ctypes.c_int, [P, I64, I64, ctypes.POINTER(I64), ctypes.POINTER(I64)]),
+        "az_solver_book_finish": (ctypes.c_int, [P]),
+        "az_solver_book_save": (ctypes.c_int, [P, ctypes.c_char_p]),
+        "az_solver_book_load": (ctypes.c_int, [P, ctypes.c_char_p]),
+        "az_solver_book_info": (ctypes.c_int, [P, ctypes.POINTER(I32), ctypes.POINTER(I32), P]),
+        "az_solver_book_level": (ctypes.c_int, [P, ctypes.c_int, I64, I64, I64, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -777,6 +787,8 @@ class ChessReplay:
 
 
 SOLVER_SOLVED, SOLVER_UNSOLVED = 0, 1
+BOOK_NONE, BOOK_BUILDING, BOOK_FINISHED = 0, 1, 2
+BOOK_NO_SCORE = -128
 
 
 class Solver:
@@ -832,6 +844,91 @@ class Solver:
         _check(self._L.az_solver_solve(self._h, _ptr(b), count, int(node_budget), _ptr(scores), _ptr(status),
                                        _ptr(nodes)))
         return scores, status, nodes
+
+    # ---- the opening book (az_solver_book_*, csrc/az_book.hip)
+    def book_begin(self, depth):
+        """Enumerates every reachable unfinished position with 0..depth stones,
+        reduced by the left-right mirror, on the device; replaces any book the
+        solver had.  -> the level counts, int64 [depth + 1]."""
+        counts = np.zeros(int(depth) + 1 if depth >= 0 else 1, np.int64)
+        _check(self._L.az_solver_book_begin(self._h, int(depth), _ptr(counts)))
+        return counts
+
+    def book_solve(self, max_positions, node_budget):
+        """Searches up to max_positions deepest-level positions that have no score
+        yet -> (remaining, unsolved): positions still without a score, and those of
+        this call whose search passed node_budget (they are tried again later)."""
+        remaining, unsolved = ctypes.c_int64(), ctypes.c_int64()
+        _check(self._L.az_solver_book_solve(self._h, int(max_positions), int(node_budget), ctypes.byref(remaining),
+                                            ctypes.byref(unsolved)))
+        return remaining.value, unsolved.value
+
+    def book_finish(self):
+        """Backs the scores up to the empty board; from here on solve() answers
+        the book's positions without a search.  AzError while positions remain."""
+        _check(self._L.az_solver_book_finish(self._h))
+
+    def book_save(self, path):
+        _check(self._L.az_solver_book_save(self._h, os.fsencode(path)))
+
+    def book_load(self, path):
+        """Replaces the solver's book by the file's; AzError naming the reason for
+        a file that is no book, of another geometry, cut short or damaged."""
+        _check(self._L.az_solver_book_load(self._h, os.fsencode(path)))
+
+    def book_info(self):
+        """-> (depth, state, level counts [depth + 1]); depth -1 and BOOK_NONE without a book."""
+        depth, state = ctypes.c_int32(), ctypes.c_int32()
+        counts = np.zeros(self.height * self.width, np.int64)
+        _check(self._L.az_solver_book_info(self._h, ctypes.byref(depth), ctypes.byref(state), _ptr(counts)))
+        return depth.value, state.value, counts[:depth.value + 1].copy()
+
+    def book_level(self, stones, first=0, count=None, stride=1):
+        """Entries first, first + stride, ... of the level with `stones` stones ->
+        (boards [count, H, W] int8, +1 the side to move; scores int8,
+        BOOK_NO_SCORE where there is none yet).  count=None: to the level's end."""
+        if count is None:
+            n = int(self.book_info()[2][stones])
+            count = max(0, (n - int(first) + int(stride) - 1) // int(stride))
+        boards = np.zeros((int(count), self.height, self.width), np.int8)
+        scores = np.zeros(int(count), np.int8)
+        _check(self._L.az_solver_book_level(self._h, int(stones), int(first), int(count), int(stride), _ptr(boards),
+                                            _ptr(scores)))
+        return boards, scores
+
+    def build_book(self, depth, node_budget, chunk=1 << 16, path=None, seconds=None, report=None):
+        """Builds the book of `depth`, or goes on with the one the solver holds
+        (book_load) when it has that depth: book_solve in chunks of `chunk`
+        positions, saved to `path` after each, then book_finish.  Stops after
+        `seconds` (checked between chunks), or when a whole pass over the
+        unsolved positions solves none of them.  report(done, remaining,
+        unsolved) is called per chunk.  -> True when the book is finished."""
+        t0 = time.perf_counter()
+        have, state, counts = self.book_info()
+        if have != depth or state == BOOK_NONE:
+            counts = self.book_begin(depth)
+            state = BOOK_BUILDING
+        if state == BOOK_FINISHED:
+            return True
+        total = int(counts[depth])
+        remaining, failed_in_a_row = None, 0
+        while remaining != 0:
+            if seconds is not None and time.perf_counter() - t0 >= seconds:
+                return False
+            before = remaining
+            remaining, unsolved = self.book_solve(chunk, node_budget)
+            if path is not None:
+                self.book_save(path)
+            if report is not None:
+                report(total - remaining, remaining, unsolved)
+            # every position left has gone over the budget since the last one was scored: give up
+            failed_in_a_row = failed_in_a_row + unsolved if before == remaining else unsolved
+            if remaining and failed_in_a_row >= remaining:
+                return False
+        self.book_finish()
+        if path is not None:
+            self.book_save(path)
+        return True
 
 
 class ChessEngine(_EngineBase):

@@ -3,15 +3,20 @@ on the device solver (engine.Solver, csrc/az_solver.hip).
 
 The reference pipes move strings to a prebuilt c4solver with a 7x6 opening
 book; here the positions are solved by libaz, any gravity board it accepts
-(W <= 16, W * (H + 1) <= 56), with the c4solver's score convention.  The one
-deviation: the reference has a book, this has a budget.  The solver is off
-until ConfigSolver.node_budget > 0 (NotImplementedError, as before), and a
-position whose search passes the budget raises SolverBudgetError.
+(W <= 16, W * (H + 1) <= 56), with the c4solver's score convention.  A
+position is searched within ConfigSolver.node_budget nodes; an opening book of
+this project's own (ConfigSolver.book_path, built by `python -m
+custom_alphazero.exact_solvers --build-book`) answers the shallow positions no
+budget reaches, as the reference's book does on 7x6.  The solver is off until
+ConfigSolver.node_budget > 0 (NotImplementedError, as before), and a position
+that is not in the book and whose search passes the budget raises
+SolverBudgetError.
 
 The three reference functions keep their names and signatures; the *_batch
 forms answer many boards from one solver call (the batched arena, the MCTS
 evaluator).
 """
+import os
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -54,13 +59,29 @@ def check_solver_config():
 
 
 def get_solver() -> az.Solver:
-    """The module-level solver of ConfigConnectN's (H, W, n) on ConfigSolver.device."""
+    """The module-level solver of ConfigConnectN's (H, W, n) on ConfigSolver.device,
+    with the opening book of ConfigSolver.book_path loaded when that is set: a
+    missing file is FileNotFoundError, a file of another geometry or a damaged
+    one engine.AzError naming which, a book whose build is not finished RuntimeError."""
     check_solver_config()
     c = ConfigConnectN
-    key = (int(c.board_height), int(c.board_width), int(c.n), int(ConfigSolver.device))
+    book_path = str(ConfigSolver.book_path or "")
+    key = (int(c.board_height), int(c.board_width), int(c.n), int(ConfigSolver.device), book_path)
     if key not in _solvers:
+        if book_path and not os.path.isfile(book_path):
+            raise FileNotFoundError(f"ConfigSolver.book_path = {book_path!r}: no such file (build it with "
+                                    f"python -m custom_alphazero.exact_solvers --build-book)")
         s = az.Solver(key[0], key[1], key[2], tt_log2=int(ConfigSolver.tt_log2), device=key[3])
-        s.configure(split_stones=int(ConfigSolver.split_stones), max_jobs=int(ConfigSolver.max_jobs))
+        try:
+            s.configure(split_stones=int(ConfigSolver.split_stones), max_jobs=int(ConfigSolver.max_jobs))
+            if book_path:
+                s.book_load(book_path)
+                if s.book_info()[1] != az.BOOK_FINISHED:
+                    raise RuntimeError(f"ConfigSolver.book_path = {book_path!r}: the book's build is not finished "
+                                       f"(go on with --build-book)")
+        except Exception:
+            s.close()
+            raise
         _solvers[key] = s
     return _solvers[key]
 

@@ -361,6 +361,43 @@ int az_solver_configure(az_solver* s, int split_stones, int64_t max_jobs, int st
 int az_solver_solve(az_solver* s, const int8_t* boards, int64_t count, int64_t node_budget,
                     int32_t* scores, uint8_t* status, int64_t* nodes);
 
+/* The solver's opening book (csrc/az_book.h, az_book.hip; DESIGN.md "Opening book"): for every t in
+ * 0..depth the reachable unfinished positions with t stones, reduced by the left-right mirror, each
+ * with its exact score.  Built on the device: begin enumerates the levels, solve scores the deepest
+ * one in chunks through the solver's search, finish backs the scores up to the empty board.  With a
+ * finished book, az_solver_solve answers every root the book holds from one lookup launch (status
+ * SOLVED, nodes 0); other roots, and a handle without a finished book, go on as before. */
+#define AZ_BOOK_NONE 0
+#define AZ_BOOK_BUILDING 1
+#define AZ_BOOK_FINISHED 2
+#define AZ_BOOK_NO_SCORE (-128)
+/* enumerates levels 0..depth (0 <= depth <= H*W - 1), replacing any book of the handle; state
+ * BUILDING.  Out: level_counts [depth + 1] */
+int az_solver_book_begin(az_solver* s, int depth, int64_t* level_counts);
+/* searches up to max_positions level-`depth` positions that have no score, node_budget nodes each;
+ * those over budget stay without one (counted in *unsolved) and are tried again only after every
+ * untried position had its turn.  *remaining: positions still without a score.  AZ_E_STATE unless
+ * BUILDING */
+int az_solver_book_solve(az_solver* s, int64_t max_positions, int64_t node_budget, int64_t* remaining,
+                         int64_t* unsolved);
+/* AZ_E_STATE while positions remain; else scores levels depth-1 .. 0 and the state is FINISHED.  A
+ * position whose child is missing or unscored is AZ_E_DEVICE ("book inconsistent"), never a score */
+int az_solver_book_finish(az_solver* s);
+/* A little-endian file: magic, version, H, W, n, depth, state, where the solve goes on, the level
+ * counts, per level the keys (uint64) and the scores (int8), and a 64-bit checksum.  A book that is
+ * still BUILDING saves and loads too: a long build spreads over processes.  load replaces the
+ * handle's book; AZ_E_INVALID naming which for a wrong magic, another geometry, a short file, a
+ * checksum mismatch, or a level whose keys are not strictly ascending */
+int az_solver_book_save(az_solver* s, const char* path);
+int az_solver_book_load(az_solver* s, const char* path);
+/* *depth -1 and *state NONE without a book; level_counts [H*W], 0 past depth */
+int az_solver_book_info(az_solver* s, int32_t* depth, int32_t* state, int64_t* level_counts);
+/* entries first, first + stride, ... (count of them, stride >= 1) of level `stones` as boards
+ * [count][H][W] int8 (row 0 the top row, +1 the side to move) and scores [count] (AZ_BOOK_NO_SCORE:
+ * none yet) */
+int az_solver_book_level(az_solver* s, int stones, int64_t first, int64_t count, int64_t stride,
+                         int8_t* boards, int8_t* scores);
+
 #ifdef __cplusplus
 }
 #endif
